@@ -14,6 +14,11 @@ compositing, depth -- plus, on N > 1 GPUs, the RCCL gather of every rank's
 repack and lin_z latent table) is redone inside every step, not cached.
 
 python bench.py [--gpus N] [--steps K] [--warmup W] [--config 3|4|5]; N > 1 via torch.distributed.run.
+A plain run sets up, warms up, times the K steps and prints the line: the rate, ms_per_step and the field roofline
+taken from HIP events inside the timed steps. --full adds every measurement that takes runs of its own: the
+rocprofv3 --pmc traffic passes, the HBM yardsticks and the per-kernel HBM replays, the config-2 / 4 / 5 and
+strict-fp32 legs and the CPU baseline (--no-pmc, --no-legs, --no-cpu-baseline leave single ones out of a --full run).
+--dump-outputs DIR writes what the last timed step returned (rgb_coarse, rgb_fine, depth) as DIR/<name>.npy.
 --config 5 (BASELINE configs[4]): a fixed 4 x 800 x 800 rays per step for the whole job, dealt to the ranks in
 64-ray tiles by avr.parallel.render_sharded and gathered with one all_gather ("scaling": "strong").
 Prints one JSON line on rank 0.
@@ -450,15 +455,19 @@ def run_train(args, device, train_pmc=None):
     gt = torch.rand(SB, R, 3, generator=g).to(device)
     opt = torch.optim.Adam(params, lr=1e-4)
 
+    last = {}   # the latest eager step's renderer outputs (--dump-outputs)
+
     def step():
         rgb_c, rgb_f, _, _ = rend(c2w, K, x_pix, net)
         loss = ((rgb_c - gt) ** 2).mean() + ((rgb_f - gt) ** 2).mean()
         opt.zero_grad()
         loss.backward()
         opt.step()
+        if args.dump_outputs:
+            last.update(rgb_coarse=rgb_c.detach(), rgb_fine=rgb_f.detach())
         return loss
 
-    res, nonfinite = {}, {}
+    res, nonfinite, dumped = {}, {}, {}
     for mode in args.train_modes.split(","):
         net.hip_backward = mode in ("hip", "hip_graph")
         run = step
@@ -493,6 +502,10 @@ def run_train(args, device, train_pmc=None):
         # no autograd graph of this mode outlives it (its AccumulateGrad nodes would carry their streams into the
         # next mode's steps, and into a capture)
         loss = loss.detach()
+        if args.dump_outputs:
+            # the captured step hands back its loss alone; an eager step also its rgb_coarse / rgb_fine
+            dumped[mode] = dict(loss=loss.clone(), **({} if mode == "hip_graph" else
+                                                      {k: v.clone() for k, v in last.items()}))
         if mode == "hip_graph":
             assert run.captures == 1 and bool(torch.isfinite(loss)), (run.captures, float(loss))
         if mode == "hip":
@@ -512,6 +525,8 @@ def run_train(args, device, train_pmc=None):
         wl = (f"train.py defaults: {SB} scenes x {R} rays, {rend.n_coarse} coarse + {rend.n_fine} fine "
               f"({rend.n_fine_depth} depth) samples, Adam lr 1e-4")
     hip_t = res["hip"] if "hip" in res else res["hip_graph"]
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, dumped["hip" if "hip" in res else "hip_graph"])
     line = {
         "metric": "training rays/s (train.py step: forward + loss.backward() + Adam through "
                   + ("AdaptiveVolumeRenderer)" if args.renderer == "adaptive" else "VolumeRenderer)"),
@@ -545,6 +560,30 @@ def run_train(args, device, train_pmc=None):
                               "--pmc-child of this train step (1 warm-up + 1 step): mfma_busy = busy cycles / "
                               "(1024 SIMDs x GRBM_GUI_ACTIVE / 8 XCDs), clock = GRBM_GUI_ACTIVE / 8 / dispatch time")
     print(json.dumps(line), flush=True)
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, outputs, limit=DUMP_LIMIT_BYTES):
+    """--dump-outputs: the last timed step's outputs (name -> tensor with the rays along dim 1, or a scalar) as
+    path/<name>.npy, float32 (float64 stays float64). Outputs that would take more than `limit` bytes together
+    are written as one fixed, seeded sample of their rays (the same sorted ray indices for every output and run)."""
+    os.makedirs(path, exist_ok=True)
+    arrs = {}
+    for name, t in outputs.items():
+        a = t.detach().cpu().numpy()
+        arrs[name] = np.asarray(a, dtype=np.float64 if a.dtype == np.float64 else np.float32, order="C")
+    total = sum(a.nbytes for a in arrs.values())
+    if total > limit:
+        per_ray = [a for a in arrs.values() if a.ndim >= 2]
+        n_rays = per_ray[0].shape[1]
+        assert all(a.shape[1] == n_rays for a in per_ray), {k: v.shape for k, v in arrs.items()}
+        keep = max(1, int(n_rays * limit // total))
+        idx = np.sort(np.random.default_rng(0).choice(n_rays, size=keep, replace=False))
+        arrs = {k: (np.ascontiguousarray(a[:, idx]) if a.ndim >= 2 else a) for k, a in arrs.items()}
+    for name, a in arrs.items():
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def _free_port():
@@ -642,6 +681,8 @@ def run_standin(args, config, world, rank):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t[0])
     phases = shard_phases(stimer, args.steps, torch.device("cpu"), R) if world > 1 else None
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, dict(zip(("rgb_coarse", "rgb_fine", "depth"), out[:3])))
     if rank == 0:
         line = {"metric": "rays/sec (128 coarse + 64 fine samples) + achieved HBM GB/s vs roofline",
                 "value": round(R * args.steps / elapsed, 1), "unit": "rays/s", "n_gpus": world, "steps": args.steps,
@@ -1012,9 +1053,15 @@ def main():
     ap.add_argument("--n-fine", type=int, default=64)
     ap.add_argument("--precision", choices=["x3", "fp32"], default="x3",
                     help="field MFMA path: split-fp16 (3 products, fp32 accumulate) or fp32")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-pmc", action="store_true", help="skip the rocprofv3 --pmc traffic leg")
-    ap.add_argument("--no-legs", action="store_true", help="skip the config-2/4/5 and fp32 legs of the N=1 line")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes runs of its own: the rocprofv3 --pmc traffic passes, the HBM "
+                         "yardsticks and per-kernel HBM replays, the config-2/4/5 and fp32 legs, the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (what the renderer call returned) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-pmc", action="store_true", help="--full: skip the rocprofv3 --pmc traffic leg")
+    ap.add_argument("--no-legs", action="store_true",
+                    help="--full: skip the config-2/4/5 and fp32 legs of the N=1 line")
     ap.add_argument("--config5-steps", type=int, default=2, help="N=1: timed steps of the config-4 / 5 legs")
     ap.add_argument("--fp32-steps", type=int, default=3, help="N=1: timed steps of the strict-fp32 leg")
     ap.add_argument("--pmc-child", action="store_true", help=argparse.SUPPRESS)
@@ -1050,7 +1097,7 @@ def main():
     args = ap.parse_args()
     if args.pmc_child:
         args.steps, args.warmup, args.no_cpu_baseline, args.no_pmc, args.no_legs = 1, 1, True, True, True
-        args.pmc_train, args.train_modes = False, "hip"
+        args.pmc_train, args.train_modes, args.dump_outputs = False, "hip", None
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(spawn_ranks(args.gpus))
@@ -1069,7 +1116,7 @@ def main():
 
     # the traffic leg runs first: its profiled children use the GPU before this process does
     pmc, pmc_note = None, "skipped"
-    if (world == 1 and args.mode == "render" and config == 3 and not args.no_pmc):
+    if (world == 1 and args.mode == "render" and config == 3 and args.full and not args.no_pmc):
         pmc, pmc_note = pmc_traffic(args)
     train_pmc = None
     if world == 1 and args.mode == "train" and args.pmc_train:
@@ -1105,8 +1152,10 @@ def main():
     shared = share_scene(net, device, use_dist)
     timer = FieldTimer()
     timer.wrap(fused)
-    hbm = HbmKernelTimer(avr.ops)
-    hbm.install()
+    hbm = None
+    if args.full:
+        hbm = HbmKernelTimer(avr.ops)
+        hbm.install()
     rend = VolumeRenderer(0.8, 1.8, args.n_coarse, args.n_fine, 0, 0.01, True)
     # config 5: one frame-wide Philox stream keyed by global ray ids (render_sharded); else a batch per rank
     rend.seed = 1234 if config == 5 else 1234 + rank
@@ -1141,6 +1190,8 @@ def main():
     def render_fn(c, k, x, ray_ids=None, n_rays_total=None):
         return rend(c, k, x, net, ray_ids=ray_ids, n_rays_total=n_rays_total)
 
+    last = {}   # what the latest step's renderer call returned (--dump-outputs)
+
     def step():
         fused._packed.clear()       # per-scene prep inside the step: repack weights (from scratch), rebuild lin_z tables
         fused._pack_args.clear()
@@ -1150,14 +1201,17 @@ def main():
                     rgb_c, rgb_f, depth, _ = render_sharded(render_fn, c2w, K, x_pix, timer=stimer)
                 else:
                     rgb_c, rgb_f, depth, _ = rend(c2w, K, x_pix, net)
+                last.update(rgb_coarse=rgb_c, rgb_fine=rgb_f, depth=depth)
                 return rgb_f
             if config == 2:   # BASELINE configs[1]: the coarse pass alone
                 ro, rd, zc, _, _ = avr.ops.rays_sample_coarse(x_pix, K, c2w, 0.8, 1.8, args.n_coarse, seed=rend.seed)
                 rgb_c, _, _ = avr.ops.composite(zc, fused.forward_rays(ro[0], rd[0], zc, True), True,
                                                 want_weights=False)
                 rend.last_path, rend.last_fine_samples = "fused", 0
+                last.update(rgb_coarse=rgb_c)
                 return rgb_c
             rgb_c, rgb_f, depth, _ = rend(c2w, K, x_pix, net)
+            last.update(rgb_coarse=rgb_c, rgb_fine=rgb_f, depth=depth)
             if use_dist:
                 local = torch.cat([rgb_c.reshape(-1), rgb_f.reshape(-1), depth.reshape(-1)])
                 dist.all_gather_into_tensor(gathered, local)
@@ -1170,7 +1224,8 @@ def main():
     timer.reset()
     if stimer is not None:
         stimer.reset()
-    hbm.on = True
+    if hbm is not None:
+        hbm.on = True
     fine_evaluated = [0]
 
     def counted_step():
@@ -1179,7 +1234,8 @@ def main():
         return out
 
     elapsed, out = time_steps(counted_step, args.steps, 0, world if use_dist else 1, device)
-    hbm.on = False
+    if hbm is not None:
+        hbm.on = False
     field_ms = timer.total_ms()
     field_launches = len(timer.events)
     field_spread = None
@@ -1191,6 +1247,8 @@ def main():
     assert bool(torch.isfinite(out).all())
     if args.pmc_child:
         return
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, last)
 
     # whole-job rays: config 5 renders a fixed 4 x 800 x 800 per step over all ranks (strong scaling)
     rays_total = (R if config == 5 else R * world) * args.steps
@@ -1286,10 +1344,11 @@ def main():
         line["roofline"]["traffic_source"] = f"not measured in this run ({pmc_note})"
     # the renderer's HBM-bound kernels (the metric's "achieved HBM GB/s vs roofline"), HIP events per launch,
     # against the 8 TB/s peak and against what a streaming copy reaches on this box
-    ach = achievable_hbm_gbs(device)
-    line["hbm_achievable_GBs"] = round(ach[0], 1)
-    line["hbm_write_achievable_GBs"] = round(ach[1], 1)
-    line["hbm_kernels"] = hbm.report(achievable=ach)
+    if hbm is not None:
+        ach = achievable_hbm_gbs(device)
+        line["hbm_achievable_GBs"] = round(ach[0], 1)
+        line["hbm_write_achievable_GBs"] = round(ach[1], 1)
+        line["hbm_kernels"] = hbm.report(achievable=ach)
     if shared is not None:
         line["scene_broadcast"] = shared
         line["scene_checksum"] = scene_checksum(net)
@@ -1302,13 +1361,13 @@ def main():
     if config == 4:
         line["config"]["fine_samples_evaluated_fraction"] = round(
             fine_evaluated[0] / (args.steps * R * (args.n_coarse + args.n_fine)), 4)
-    if world == 1 and config == 3 and not args.no_legs:
+    if world == 1 and config == 3 and args.full and not args.no_legs:
         line["config2"] = config2_leg(args, net, fused, K, c2w, x_pix, device)
         line["config4"] = config4_leg(args, net, K, device)
         line["config5"] = config5_leg(args, net, fused, K, device)
         if args.precision == "x3":
             line["fp32"] = fp32_leg(args, net, fused, timer, K, c2w, x_pix, device)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         line["cpu_baseline"] = cpu_baseline()
     if rank == 0:
         print(json.dumps(line), flush=True)

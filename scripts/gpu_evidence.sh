@@ -3,7 +3,7 @@
 # time limit; the first failure ends the script.
 #   tests  the whole -m gpu suite in one process (per-test timeout)       -> $OUT/pytest_gpu.log
 #   smoke  __graft_entry__.smoke()                                        -> $OUT/smoke.log
-#   bench  the default bench line (legs, PMC traffic, CPU baseline)        -> $OUT/bench.log
+#   bench  the bench.py --full line (legs, PMC traffic, CPU baseline)      -> $OUT/bench.log
 #   prof   rocprofv3 --kernel-trace --stats of a short bench command        -> $OUT/bench_kernel_stats.csv
 #   train  bench.py --mode train for each conf in CONFS (+ TRAIN_ARGS)      -> $OUT/bench_train_<conf>.log
 #   tprof  rocprofv3 kernel stats of the HIP train step (CONFS' last conf)  -> $OUT/train_kernel_stats.csv
@@ -30,7 +30,7 @@ if has smoke; then
   rc=$?; tail -1 $OUT/smoke.log; [ $rc -eq 0 ] || { echo "smoke rc=$rc"; exit $rc; }
 fi
 if has bench; then
-  timeout -k 10 600 python -u bench.py ${BENCH_ARGS:-} > $OUT/bench.log 2> $OUT/bench.err
+  timeout -k 10 600 python -u bench.py --full ${BENCH_ARGS:-} > $OUT/bench.log 2> $OUT/bench.err
   rc=$?; tail -c 600 $OUT/bench.log; echo; [ $rc -eq 0 ] || { echo "bench rc=$rc"; tail -5 $OUT/bench.err; exit $rc; }
 fi
 if has prof; then

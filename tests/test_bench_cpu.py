@@ -56,6 +56,37 @@ def test_bench_default_is_config3_weak():
     assert one["scaling"] == "weak" and one["n_gpus"] == 1
 
 
+def test_bench_dump_outputs_repeats(tmp_path):
+    """--dump-outputs writes the last timed step's outputs as float32 .npy, the same from run to run, and the line
+    carries ms_per_step for the steps asked for."""
+    import numpy as np
+    dirs = [str(tmp_path / d) for d in ("a", "b")]
+    for d in dirs:
+        one = _line(_bench("--gpus", "1", "--frame", "32", "--steps", "3", "--warmup", "1", "--dump-outputs", d))
+        assert one["steps"] == 3 and one["ms_per_step"] > 0
+    assert sorted(os.listdir(dirs[0])) == ["depth.npy", "rgb_coarse.npy", "rgb_fine.npy"]
+    for f in os.listdir(dirs[0]):
+        a, b = np.load(os.path.join(dirs[0], f)), np.load(os.path.join(dirs[1], f))
+        assert a.dtype == np.float32 and a.shape[1] == 32 * 32 and np.array_equal(a, b)
+
+
+def test_dump_outputs_samples_rays_over_the_limit(tmp_path):
+    """Outputs over the byte limit are written as one seeded sample of rays: the same rays of every output."""
+    import numpy as np
+    import torch
+    from bench import dump_outputs
+    R = 1000
+    ids = torch.arange(R, dtype=torch.float32)
+    outs = {"rgb": ids.reshape(1, R, 1).expand(1, R, 3), "depth": ids.reshape(1, R), "loss": torch.tensor(2.5)}
+    for d in ("a", "b"):
+        dump_outputs(str(tmp_path / d), outs, limit=4000)
+    rgb, depth = np.load(tmp_path / "a" / "rgb.npy"), np.load(tmp_path / "a" / "depth.npy")
+    assert rgb.nbytes + depth.nbytes + 4 <= 4000 and depth.shape[1] > 200
+    assert np.array_equal(rgb[0, :, 0], depth[0]) and np.all(np.diff(depth[0]) > 0)
+    assert float(np.load(tmp_path / "a" / "loss.npy")) == 2.5
+    assert np.array_equal(depth, np.load(tmp_path / "b" / "depth.npy"))
+
+
 def test_bench_rejects_world_size_mismatch():
     p = _bench("--gpus", "2", "--steps", "1", env_extra={"WORLD_SIZE": "1", "RANK": "0", "LOCAL_RANK": "0"})
     assert p.returncode != 0 and "WORLD_SIZE=1" in (p.stderr + p.stdout)
