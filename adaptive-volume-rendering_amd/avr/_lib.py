@@ -15,7 +15,7 @@ LIB_PATH = os.environ.get("AVR_LIB_PATH") or os.path.join(_HERE, "libavr_hip.so"
 AVR_MAX_BLOCKS = 8
 AVR_MAX_SCENES = 16
 AVR_LOOKUP_GRAD_TERMS = 8
-ABI_VERSION = 16
+ABI_VERSION = 17
 
 c_float_p = ctypes.POINTER(ctypes.c_float)
 c_void_p = ctypes.c_void_p
@@ -160,6 +160,13 @@ _SIGS = {
                              c_void_p],
     "avr_lin_out_act_bwd_rows": [i64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
     "avr_spade_bwd_rows": [i64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
+    "avr_loss_workspace_bytes": [i64, ctypes.POINTER(i64)],
+    "avr_loss_fwd": [i64, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_float, c_void_p, i64, c_void_p,
+                     c_void_p],
+    "avr_loss_bwd": [i64, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_float, c_void_p, c_void_p,
+                     c_void_p, c_void_p, c_void_p, c_void_p],
+    "avr_image_metrics_workspace_bytes": [i64, c_int, c_int, ctypes.POINTER(i64)],
+    "avr_image_metrics": [c_void_p, c_void_p, i64, c_int, c_int, c_void_p, i64, c_void_p, c_void_p, c_void_p],
     "avr_stream_copy": [c_void_p, c_void_p, i64, c_void_p],
     "avr_stream_fill": [c_void_p, i64, c_uint32, c_void_p],
 }

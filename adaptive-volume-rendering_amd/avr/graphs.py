@@ -127,7 +127,8 @@ class GraphedTrainStep:
     microseconds each).
 
     step_fn() runs one step on tensors the caller keeps at fixed addresses (refill them in place between calls)
-    and returns what the caller reads after the step (e.g. the loss); it may call optimizer.zero_grad() (the
+    and returns what the caller reads after the step (e.g. the loss; avr.losses.loss_fn is train.py's loss without
+    the reference's host-side isnan test, which a capture refuses); it may call optimizer.zero_grad() (the
     default set_to_none: a host-only no-op once captured: the captured backward writes the gradients). The
     optimizer must be capturable: torch.optim.Adam(..., capturable=True, fused=True) (the fused form is one
     multi-tensor kernel; the capturable foreach form adds many small launches).

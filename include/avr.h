@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define AVR_ABI_VERSION 16
+#define AVR_ABI_VERSION 17
 #define AVR_MAX_BLOCKS 8
 #define AVR_LOOKUP_GRAD_TERMS 8   /* tables per avr_latent_tables_grad_points call */
 #define AVR_MAX_SCENES 16   /* scenes per training-forward launch */
@@ -547,6 +547,47 @@ int avr_raymarch_bwd(const avr_view_desc* views, int n_scenes, const float* gate
                      const float* w_out, const float* rd, const float* trace, const float* state,
                      const float* grad_world, int64_t n_per_scene, int steps, int lookup_grad, float* d_tables,
                      float* d_grads, void* scratch, int64_t scratch_bytes, void* stream);
+
+/* ------------------------------------------------- training loss and metrics
+ * ABI 17: loss_fn (utils.py:364-377) over n_rays rays without a host sync, so it can be recorded in a HIP-graph
+ * capture. terms = AVR_LOSS_COARSE | AVR_LOSS_FINE | AVR_LOSS_DEPTH selects
+ *   loss = [mean((rgb_c - gt)^2)] + [mean((rgb_f - gt)^2)] + [10000 mean(max(near - d, 0) + max(d - far, 0))]
+ * (--loss_mode coarse | fine | both, --depth_regularization); rgb_c, rgb_f, gt (n_rays, 3) and depth (n_rays) as
+ * the renderers return them; the pointer of a term that is not selected is not read. If the MSE part (the sum of
+ * the selected MSEs) is NaN it becomes 1e-6 and every rgb gradient exactly 0 (the reference's `if loss.isnan()`,
+ * decided on the device); the penalty is added and differentiated as usual, and a non-finite depth propagates.
+ * Forward: one pass, every difference, square and sum in fp64, the workgroups' partials added in a fixed order
+ * (no floating-point atomics: bit-identical from run to run) -> record[4] = {loss, mse_c, mse_f, penalty} (the
+ * MSEs as summed, NaN included; 0 for a term not selected). `workspace` holds avr_loss_workspace_bytes(n_rays)
+ * bytes (the partials; may be NULL where one workgroup covers n_rays). One launch, two above 2730 rays.
+ * Backward, one launch: grad_rgb_c / grad_rgb_f (n_rays, 3) = g 2 (rgb - gt) / (3 n_rays), or 0 under the NaN rule
+ * read from the forward's record; grad_depth (n_rays) = g 10000 / n_rays (c(d - far) - c(near - d)) with c(t) = 1
+ * for t > 0, 0.5 at t == 0 (torch.max's backward at a tie) and 0 below; g = grad_loss[0], a DEVICE scalar. A NULL
+ * gradient pointer is skipped. n_rays == 0 is a no-op; null pointers of selected terms and a selection without
+ * AVR_LOSS_COARSE or AVR_LOSS_FINE are refused before any HIP call.                                              */
+#define AVR_LOSS_COARSE 1
+#define AVR_LOSS_FINE 2
+#define AVR_LOSS_DEPTH 4
+int avr_loss_workspace_bytes(int64_t n_rays, int64_t* n_bytes);
+int avr_loss_fwd(int64_t n_rays, int terms, const float* rgb_c, const float* rgb_f, const float* depth,
+                 const float* gt, float near_, float far_, void* workspace, int64_t workspace_bytes, float* record,
+                 void* stream);
+int avr_loss_bwd(int64_t n_rays, int terms, const float* rgb_c, const float* rgb_f, const float* depth,
+                 const float* gt, float near_, float far_, const float* record, const float* grad_loss,
+                 float* grad_rgb_c, float* grad_rgb_f, float* grad_depth, void* stream);
+
+/* ABI 17: PSNR and SSIM of n_frames pairs of (height, width, 3) frames, pixel-major and channel-innermost -- what
+ * get_metrics (utils.py:431-461) asks of skimage.metrics with data_range = 1: psnr[f] = 10 log10(1 / mse) over all
+ * height * width * 3 values (+inf for identical frames); ssim[f] = structural_similarity(channel_axis=-1): per
+ * channel the 7 x 7 uniform-window means, sample covariances (49/48), C1 = 1e-4, C2 = 9e-4, S averaged over the
+ * window positions inside the frame (the 3-pixel border cropped), then over the channels. Moments and S in fp64
+ * (products of fp32 values are exact there); the tiles' fp64 partials of S and of the squared error are added in
+ * a fixed order (bit-identical from run to run). `workspace` holds avr_image_metrics_workspace_bytes() bytes.
+ * Two launches (every tile of every frame, then one wave per frame). height, width >= 7; n_frames == 0 is a
+ * no-op; sizes and null pointers are checked before any HIP call.                                              */
+int avr_image_metrics_workspace_bytes(int64_t n_frames, int height, int width, int64_t* n_bytes);
+int avr_image_metrics(const float* img, const float* gt, int64_t n_frames, int height, int width, void* workspace,
+                      int64_t workspace_bytes, float* psnr, float* ssim, void* stream);
 
 /* ------------------------------------------------------------ measurement
  * Streaming device copy dst[0, n_bytes) = src[0, n_bytes) (16-B aligned,
