@@ -17,6 +17,13 @@ AVR_MAX_SCENES = 16
 AVR_LOOKUP_GRAD_TERMS = 8
 ABI_VERSION = 17
 
+
+def scene_groups(n):
+    """(first scene, count) of each multi-scene launch over scenes 0 .. n-1: count <= AVR_MAX_SCENES."""
+    for g0 in range(0, n, AVR_MAX_SCENES):
+        yield g0, min(AVR_MAX_SCENES, n - g0)
+
+
 c_float_p = ctypes.POINTER(ctypes.c_float)
 c_void_p = ctypes.c_void_p
 i64 = ctypes.c_int64
@@ -30,6 +37,13 @@ class FieldDims(ctypes.Structure):
     _fields_ = [("d_in", c_int), ("d_latent", c_int), ("d_hidden", c_int), ("n_blocks", c_int),
                 ("n_lin_z", c_int), ("num_freqs", c_int), ("freq_factor", c_float), ("precision", c_int),
                 ("bn", c_int), ("spade", c_int), ("beta", c_float)]
+
+    def with_precision(self, precision):
+        """A by-value copy selecting the `precision` kernels (what a library call is given: the struct a blob was
+        packed with is never written to pick a kernel)."""
+        copy = FieldDims.from_buffer_copy(self)
+        copy.precision = precision
+        return copy
 
 
 FIELD_FP32 = 0

@@ -21,8 +21,11 @@ import ctypes
 
 import torch
 
-from . import _lib
+from . import _lib, ops
 from ._lib import BnLayer, call, ptr, stream_of
+from .field import fused_eligible, softplus_beta, train_param_names, uses_bn
+from .train_common import (forward_train, input_grads_via_autograd, lin_z_epilogue, lookup_features,
+                           padded_z_features)
 
 F32 = torch.float32
 
@@ -35,7 +38,6 @@ def bn_train_eligible(net):
     """A NewPixelNeRFNet the BatchNorm training path runs: the fused field's configuration (avr.field.
     fused_eligible, one source view) except that every ResnetFC uses bn=True with its BatchNorm in training
     mode (batch statistics), ReLU, no use_spade, d_latent a multiple of 64 up to 512 (x3 lin_z tables)."""
-    from .field import fused_eligible, uses_bn, softplus_beta
     try:
         mlps = [net.mlp_coarse] + ([net.mlp_fine] if net.mlp_fine is not None else [])
         if not all(uses_bn(m) and all(blk.bn for blk in m.blocks) for m in mlps):
@@ -113,7 +115,6 @@ def _bn_stats(bn, part, M, H, stats, stream):
 
 
 def train_param_names_bn(mlp):
-    from .field import train_param_names
     names = train_param_names(mlp)
     for b in range(mlp.n_blocks):
         names += [f"blocks.{b}.bn_0.weight", f"blocks.{b}.bn_0.bias"]
@@ -122,11 +123,7 @@ def train_param_names_bn(mlp):
 
 def forward_train_bn(fused, xyz, viewdirs, coarse):
     """The rf(xyz, viewdirs, coarse) protocol for a training-mode BatchNorm net (autograd when enabled)."""
-    mlp = fused._mlp(coarse)
-    names = train_param_names_bn(mlp)
-    named, _, _ = fused._state(mlp)
-    params = [named[n] for n in names]
-    return _FieldTrainBN.apply(fused, coarse, names, xyz, viewdirs, fused.net.encoder.latent, *params)
+    return forward_train(fused, xyz, viewdirs, coarse, _FieldTrainBN, train_param_names_bn)
 
 
 class _FieldTrainBN(torch.autograd.Function):
@@ -135,12 +132,11 @@ class _FieldTrainBN(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, fused, coarse, names, xyz, viewdirs, latent, *params):
-        from .ops import lin_out_rows
         net = fused.net
         mlp = fused._mlp(coarse)
         P = dict(zip(names, params))
         entry = fused.packed(coarse, bn_fold=False)
-        dims = entry.dims
+        dims = entry.dims.with_precision(_lib.FIELD_X3)
         H, nb, nz = dims.d_hidden, dims.n_blocks, dims.n_lin_z
         SB, B, _ = xyz.shape
         M = SB * B
@@ -151,22 +147,12 @@ class _FieldTrainBN(torch.autograd.Function):
                              f"got {M} rows)")
         with torch.no_grad():
             # lin_in's input: z_feature rows padded to 16 B (the fused kernels' zf layout)
-            zf = net.z_features(xyz.detach(), viewdirs.detach()).to(F32)
-            d_in = zf.shape[1]
-            zs = d_in + (-d_in) % 4
-            zfp = torch.zeros(M, zs, device=dev, dtype=F32)
-            zfp[:, :d_in] = zf
+            zfp, d_in, zs = padded_z_features(net, xyz, viewdirs)
             # lin_z[b](latent features) rows: gathered from the per-texel tables in the layer epilogues
             tables = fused.tables_batch(coarse, SB, fast=True, bn_fold=False)
             views = fused.views(range(SB))
             p = xyz.detach().to(F32).contiguous()
-
-            def lin_z(b):
-                """avr_bn_layer fields adding lin_z[b](latent features) rows (none past the last lin_z)."""
-                if b >= nz:
-                    return {}
-                return dict(lin_z_table=tables[0, b], lin_z_scene_stride=tables.stride(0), xyz=p,
-                            views=ctypes.addressof(views), n_views=SB, rows_per_scene=B)
+            lin_z = lambda b: lin_z_epilogue(tables, b, nz, p, views, SB, B)   # noqa: E731
             # biases with the lin_z biases folded where the tables (no bias) are added
             lz_b = [P[f"lin_z.{b}.bias"].detach() for b in range(nz)]
             b_in = P["lin_in.bias"].detach() + (lz_b[0] if nz > 0 else 0)
@@ -202,7 +188,7 @@ class _FieldTrainBN(torch.autograd.Function):
                                   **lin_z(b + 1)), stream)
             # lin_out on relu(x) (4 outputs; models.py:592), sigmoid rgb / relu sigma (models.py:856-862), and
             # max relu(x) for its weight gradient's scale (relu(x) itself is not stored)
-            out, a_max = lin_out_rows(X[nb], P["lin_out.weight"].detach(), P["lin_out.bias"].detach())
+            out, a_max = ops.lin_out_rows(X[nb], P["lin_out.weight"].detach(), P["lin_out.bias"].detach())
             out = out.reshape(SB, B, 4)
         ctx.fused, ctx.coarse, ctx.names, ctx.entry = fused, coarse, names, entry
         ctx.keep = (X, N, amax, a_max, zfp, st1, st2, betas)
@@ -211,14 +197,13 @@ class _FieldTrainBN(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, grad_out):
-        from .ops import _max_bits, lin_out_rows_bwd, sum_of_products, weight_grads
         xyz, viewdirs, latent, out, *params = ctx.saved_tensors
         fused, entry, names = ctx.fused, ctx.entry, ctx.names
         X, N, amax, a_max, zfp, st1, st2, betas = ctx.keep
         ctx.keep = None
         net = fused.net
         P = dict(zip(names, params))
-        dims = entry.dims
+        dims = entry.dims.with_precision(_lib.FIELD_X3)
         H, nb, nz = dims.d_hidden, dims.n_blocks, dims.n_lin_z
         SB, B, _ = xyz.shape
         M = SB * B
@@ -232,13 +217,13 @@ class _FieldTrainBN(torch.autograd.Function):
             bwd = fused.packed_bwd(ctx.coarse, entry)
             Gx = torch.empty(nb + 1, M, H, device=dev, dtype=F32)      # d loss / d X[k]
             # the activations' backward (d4), lin_out^T and its relu's backward (g where X > 0, else 0) in one pass
-            d4, _, d4_max = lin_out_rows_bwd(grad_out.reshape(M, 4), out.reshape(M, 4), P["lin_out.weight"].detach(),
-                                             X[nb], g=Gx[nb])
+            d4, _, d4_max = ops.lin_out_rows_bwd(grad_out.reshape(M, 4), out.reshape(M, 4),
+                                                 P["lin_out.weight"].detach(), X[nb], g=Gx[nb])
             # Gx[k] maxima (k = 0..nb): Gx[nb]'s published by fc_1[nb-1]^T's operand pass, the others by the GRAD
             # prologues that build them and avr_bn_grad_rows
             gmax = torch.zeros(2 * nb + 2, device=dev, dtype=torch.int32)
             if nb == 0:
-                gmax[0:1] = _max_bits(Gx[0])
+                gmax[0:1] = ops._max_bits(Gx[0])
             DN = torch.empty(max(nb, 1), M, H, device=dev, dtype=F32)  # d loss / d fc_0 output (pre-BN)
             dn_max = torch.zeros(max(nb, 1), device=dev, dtype=torch.int32)
             gp2 = torch.empty(M, H, device=dev, dtype=F32)
@@ -280,15 +265,8 @@ class _FieldTrainBN(torch.autograd.Function):
             # weight gradients: fc_0 (DN, relu(bn_0(X[b]))), fc_1 (Gx[b+1], relu(bn_0(N[b]))) -- both operands
             # rebuilt from the pre-BN rows in the kernel's staging --, lin_z (Gx[b], latent features),
             # lin_in (Gx[0], z_feature), lin_out (d4, relu(X[nb]))
-            lat_feat = torch.empty(M, net.d_latent, device=dev, dtype=F32)
             if nz > 0:
-                hwc = fused.latent_hwc_all(latent) if SB <= latent.shape[0] else None
-                p = xyz.detach().to(F32).contiguous()
-                for s in range(SB):
-                    li = min(s, latent.shape[0] - 1)
-                    lh = hwc[li] if hwc is not None else fused.latent_hwc(latent, li)
-                    call("avr_latent_features", ctypes.byref(fused.view(s)), ptr(lh), net.d_latent, ptr(p[s]), B,
-                         ptr(lat_feat[s * B:(s + 1) * B]), stream)
+                lat_feat = lookup_features(fused, latent, xyz.detach().to(F32).contiguous(), SB, B)
             lat_max = fused.latent_max_bits(latent)
             layers = []
             for b in range(nb):
@@ -298,10 +276,10 @@ class _FieldTrainBN(torch.autograd.Function):
                                (st2[b].mu, st2[b].scale, betas[b])))
             for b in range(nz):
                 layers.append((Gx[b], lat_feat, gmax[b:b + 1], lat_max, True))
-            zf_max = _max_bits(zfp)
+            zf_max = ops._max_bits(zfp)
             layers.append((Gx[0], zfp, gmax[0:1], zf_max, True))
             layers.append((d4, X[nb], d4_max, a_max, True, "relu"))   # relu(X[nb]) rebuilt in the staging
-            res = weight_grads(layers, M)
+            res = ops.weight_grads(layers, M)
             grads = {"lin_out.weight": res[-1][0], "lin_out.bias": res[-1][1]}
             w_in, b_in = res[-2]
             grads["lin_in.weight"], grads["lin_in.bias"] = w_in[:, :net.d_in].contiguous(), b_in
@@ -312,24 +290,11 @@ class _FieldTrainBN(torch.autograd.Function):
                 grads[f"blocks.{b}.bn_0.bias"] = dbet[b]
             for b in range(nz):
                 grads[f"lin_z.{b}.weight"], grads[f"lin_z.{b}.bias"] = res[2 * nb + b]
-        d_latent = d_xyz = None
-        if want_latent or want_xyz:
-            with torch.enable_grad():
-                lat = latent.detach().requires_grad_(want_latent)
-                x = xyz.detach().requires_grad_(want_xyz)
-                feat, zft = net.mlp_inputs(x, viewdirs.detach(), latent=lat)
-                outs, grads_out = [], []
-                if nz > 0 and not net.stop_encoder_grad:   # a detached lookup (models.py:810-811) carries none
-                    outs.append(feat)
-                    grads_out.append(sum_of_products([(Gx[b], P[f"lin_z.{b}.weight"].detach()) for b in range(nz)]))
-                if want_xyz:
-                    outs.append(zft)
-                    grads_out.append(Gx[0] @ P["lin_in.weight"].detach())
-                wrt = ([lat] if want_latent else []) + ([x] if want_xyz else [])
-                res_in = torch.autograd.grad(outs, wrt, grads_out, allow_unused=True)
-            if want_latent:
-                d_latent = res_in[0] if res_in[0] is not None else torch.zeros_like(latent)
-            if want_xyz:
-                d_xyz = res_in[-1] if res_in[-1] is not None else torch.zeros_like(xyz)
+        g_feat = g_zf = None
+        if (want_latent or want_xyz) and nz > 0 and not net.stop_encoder_grad:   # a detached lookup carries none
+            g_feat = ops.sum_of_products([(Gx[b], P[f"lin_z.{b}.weight"].detach()) for b in range(nz)])
+        if want_xyz:
+            g_zf = Gx[0] @ P["lin_in.weight"].detach()
+        d_latent, d_xyz = input_grads_via_autograd(net, xyz, viewdirs, latent, want_latent, want_xyz, g_feat, g_zf)
         return (None, None, None, d_xyz, None, d_latent) + tuple(
             grads[n] if ctx.needs_input_grad[6 + i] else None for i, n in enumerate(names))

@@ -7,17 +7,25 @@ avr_field_fwd_points). Packed weights and tables are cached and rebuilt when a
 parameter or the latent changes (tensor version counters), so an inference
 loop over many frames of one scene pays for them once, as the reference pays
 for encode() once.
+
+Every cache entry is one _Record(key, value, keep, stamp) behind _cached: a hit under the same key joins the
+reading stream to the maker's (_join), a miss builds, stamps (_stamp) and stores. A packed blob (_Packed) declares
+what hangs off it (backward blob, per-scene and batched lin_z tables) and hands each library call a by-value copy
+of its dims for the kernel precision the call means (dims_as): the cached struct is never written. _FieldTrain
+shares its entry, latent lookup and autograd tail with avr.bn_train / avr.layer_train (avr.train_common).
 """
 import collections
 import ctypes
 import os
+import typing
 import weakref
 
 import torch
 from torch.optim.optimizer import register_optimizer_step_post_hook
 
-from . import _lib
-from ._lib import FieldDims, ResnetFCWeights, ViewDesc, call, ptr, require_device, stream_of
+from . import _lib, ops, train_common
+from ._lib import FieldDims, ResnetFCWeights, ViewDesc, call, ptr, require_device, scene_groups, stream_of
+from .train_common import input_grads_via_autograd, lookup_features
 
 F32 = torch.float32
 
@@ -114,21 +122,6 @@ def _freq_factor(code):
     return float(ff)
 
 
-class _precision:
-    """dims.precision set for one library call and restored after it."""
-
-    def __init__(self, dims, value):
-        self.dims, self.value = dims, value
-
-    def __enter__(self):
-        self.saved = self.dims.precision
-        self.dims.precision = self.value
-
-    def __exit__(self, *exc):
-        self.dims.precision = self.saved
-        return False
-
-
 # Submodule (re)registrations anywhere in the process, numbered, with the id of the module that registered: a
 # FusedField._state slot is rebuilt after a registration under its MLP, so a module replaced in an MLP
 # (mlp.lin_in = nn.Linear(...)) is seen, and only then (modules built elsewhere, e.g. per training step, leave it
@@ -188,8 +181,9 @@ def _version_key(tensors, gen=True):
 
 
 def _stamp(t):
-    """(stream, event) marking the current stream's work that filled the cached device tensor t (None on the CPU
-    or while a HIP graph is being captured: one stream then, nothing to join)."""
+    """(stream, event) marking the current stream's work that filled the cached device tensor t. None on the CPU,
+    and None while a HIP graph is being captured: a value made during a capture is read without a join, also by
+    the adaptive renderer's side stream inside the graph (the open ADVICE.md finding; its fix is here and in _join)."""
     if t is None or not t.is_cuda or torch.cuda.is_current_stream_capturing():
         return None
     s = torch.cuda.current_stream(t.device)
@@ -213,17 +207,55 @@ def _join(stamp, *tensors):
             t.record_stream(s)
 
 
-class _Packed:
-    def __init__(self, dims, packed, table_keys):
-        self.dims = dims
-        self.packed = packed
-        self.tables = {}
-        self.bwd = None
-        self.bwd_stamp = None
-        self.stamp = None
+class _Record(typing.NamedTuple):
+    """One cache entry: the comparable key it was built under, the value, whatever must stay alive for the key
+    to stay sound (a tensor whose address is part of it), and the _stamp of the value's maker."""
+    key: object
+    value: object
+    keep: object = None
+    stamp: object = None
+
+
+def _hit(rec, key):
+    """True when rec holds a value built under `key`; the current stream is then joined to its maker's."""
+    if rec is None or rec.key != key:
+        return False
+    _join(rec.stamp, rec.value)
+    return True
+
+
+def _cached(store, slot, key, make, keep=None, device=True):
+    """store[slot]'s value if it was built under `key`, else make() stored in its place (the cache protocol of
+    every FusedField cache; device=False: a host-side value, nothing to stamp or join)."""
+    rec = store.get(slot)
+    if not _hit(rec, key):
+        value = make()
+        rec = store[slot] = _Record(key, value, keep, _stamp(value) if device else None)
+    return rec.value
 
 
 PRECISIONS = {"fp32": _lib.FIELD_FP32, "x3": _lib.FIELD_X3}
+
+
+class _Packed:
+    """One packed ResnetFC: dims (the struct avr_field_pack was called with) and the blob, the weight pointers
+    with the tensors behind them, and what is derived from the blob and dies with it: the backward blob (a
+    _Record or None), the per-scene lin_z tables (sb -> _Record) and the batched ones (fast -> _Record)."""
+
+    def __init__(self, dims, packed, weights=None, keep=None):
+        self.dims = dims
+        self.packed = packed
+        self.weights = weights
+        self.keep = keep
+        self.bwd = None
+        self.tables = {}
+        self.batch_tables = {}
+        self._dims_as = {precision: dims.with_precision(precision) for precision in PRECISIONS.values()}
+
+    def dims_as(self, precision):
+        """A copy of dims selecting the `precision` kernels (_lib.FIELD_X3 / _lib.FIELD_FP32): what a library
+        call is given, so that dims itself keeps describing the blob."""
+        return self._dims_as[precision]
 
 
 def n_tables(dims):
@@ -240,11 +272,13 @@ class FusedField:
             raise ValueError(f"precision must be one of {sorted(PRECISIONS)}")
         self.precision = precision
         self.net = net
-        self._packed = {}     # coarse(bool) -> (key, _Packed)
-        self._pack_args = {}  # coarse(bool) -> (pointer key, blob floats, ResnetFCWeights, kept tensors)
-        self._view_cache = {}
+        # the caches: slot -> _Record, read and filled by _cached (packed() alone keeps its own body)
+        self._packed = {}         # coarse, or (coarse, "bn_train") -> _Record of a _Packed (tables hang off it)
+        self._view_cache = {}     # (sb, ns) -> ViewDesc (view())
         self._views_cache = {}    # (range, ns) -> ViewDesc arrays (views())
         self._latent_cache = {}   # per latent version: channels-last copies, max |latent| (both MLPs share them)
+        # not a _Record: the last build's pack arguments, reused while the weight pointers stay (packed())
+        self._pack_args = {}      # slot of _packed -> (pointer key, blob floats, ResnetFCWeights, kept tensors)
         # mlp (weakly) -> ([(name, owner dict, key)] params, [...] float buffers, generation, ids of its modules)
         self._slots = weakref.WeakKeyDictionary()
 
@@ -265,14 +299,15 @@ class FusedField:
         what a captured HIP graph reads (avr.graphs.GraphedRenderer keeps references to them, so an eager call
         that replaces a cache entry cannot free memory a replay still reads)."""
         out = []
-        for _, entry in self._packed.values():
+        for rec in self._packed.values():
+            entry = rec[1]
             if entry is None:
                 continue
             out.append(entry.packed)
-            if getattr(entry, "bwd", None) is not None:
-                out.append(entry.bwd)
-            out += [hit[1] for hit in entry.tables.values()]
-            out += [hit[1] for hit in entry.__dict__.get("batch_tables", {}).values()]
+            if entry.bwd is not None:
+                out.append(entry.bwd.value)
+            out += [r.value for r in entry.tables.values()]
+            out += [r.value for r in entry.batch_tables.values()]
         return out
 
     def _latent_cached(self, what, latent, make):
@@ -280,19 +315,11 @@ class FusedField:
         # fixed or encoder-produced map keeps its copies across steps (its version counter sees in-place writes)
         gen = _PARAM_GEN[0] if (latent.is_leaf and latent.requires_grad) else (-1, _EXPLICIT_GEN[0])
         key = (gen, latent.data_ptr(), latent._version, tuple(latent.shape))
-        hit = self._latent_cache.get(what)
-        if hit is not None and hit[0] == key:
-            _join(hit[3], hit[1])
-            return hit[1]
-        val = make()
-        # holding `latent` keeps its address from being reused
-        self._latent_cache[what] = (key, val, latent, _stamp(val))
-        return val
+        return _cached(self._latent_cache, what, key, make, keep=latent)   # held: its address is in the key
 
     def latent_hwc(self, latent, s):
         """Scene s's latent map channels-last (avr_latent_features' operand), once per latent version."""
-        from .ops import latent_hwc
-        return self._latent_cached(("hwc", s), latent, lambda: latent_hwc(latent[s]))
+        return self._latent_cached(("hwc", s), latent, lambda: ops.latent_hwc(latent[s]))
 
     def latent_hwc_all(self, latent):
         """Every scene's latent map channels-last, (SB, H*W, C), once per latent version."""
@@ -303,8 +330,7 @@ class FusedField:
 
     def latent_max_bits(self, latent):
         """max |latent| as int32 float bits (the lin_z weight gradients' X scale), once per latent version."""
-        from .ops import _max_bits
-        return self._latent_cached("max", latent, lambda: _max_bits(latent))
+        return self._latent_cached("max", latent, lambda: ops._max_bits(latent))
 
     # ----------------------------------------------------------- parameters
     def _state(self, mlp):
@@ -349,10 +375,10 @@ class FusedField:
         # (avr_field_pack), and net.fused() switches a FusedField's precision in place
         slot = coarse if bn_fold else (coarse, "bn_train")
         key = (id(mlp), self.precision if bn_fold else "x3", _version_key(params))
-        hit = self._packed.get(slot)
-        if hit is not None and hit[0] == key:
-            _join(hit[1].stamp, hit[1].packed)
-            return hit[1]
+        rec = self._packed.get(slot)
+        if rec is not None and rec.key == key:
+            _join(rec.stamp, rec.value.packed)
+            return rec.value
         dims = self.dims(mlp)
         if not bn_fold:
             dims.bn, dims.precision = 0, _lib.FIELD_X3
@@ -364,13 +390,23 @@ class FusedField:
         args = self._pack_args.get(slot)
         if args is not None and args[0] == args_key:
             _, n, w, keep = args
-            packed = torch.empty(n, device=params[0].device, dtype=F32)
-            call("avr_field_pack", ctypes.byref(dims), ctypes.byref(w), ptr(packed), stream_of(packed))
-            return self._store_packed(slot, key, dims, packed, keep, w)
+        else:
+            n, w, keep, in_place = self._pack_weights(mlp, dims)
+            if in_place:
+                self._pack_args[slot] = (args_key, n, w, keep)
+            else:
+                self._pack_args.pop(slot, None)
+        packed = torch.empty(n, device=params[0].device, dtype=F32)
+        call("avr_field_pack", ctypes.byref(dims), ctypes.byref(w), ptr(packed), stream_of(packed))
+        entry = _Packed(dims, packed, w, keep)
+        self._packed[slot] = _Record(key, entry, None, _stamp(packed))
+        return entry
+
+    def _pack_weights(self, mlp, dims):
+        """avr_field_pack's arguments for mlp: (blob floats, weight pointers, the tensors behind them, whether every
+        pointer is a parameter or buffer read in place)."""
         n = ctypes.c_int64(0)
         _lib.check(_lib.load().avr_field_packed_floats(ctypes.byref(dims), ctypes.byref(n)), "avr_field_packed_floats")
-        dev = params[0].device
-        packed = torch.empty(n.value, device=dev, dtype=F32)
         w = ResnetFCWeights()
         keep = []
         derived = [False]
@@ -403,55 +439,37 @@ class FusedField:
             if dims.spade:   # scale_z[b](z) * x + lin_z[b](z) (models.py:585-587): both as per-texel tables
                 w.scale_z_w[b], w.scale_z_b[b] = P(mlp.scale_z[b].weight), P(mlp.scale_z[b].bias)
         require_device(*keep)
-        call("avr_field_pack", ctypes.byref(dims), ctypes.byref(w), ptr(packed), stream_of(packed))
-        if dims.bn or derived[0]:
-            self._pack_args.pop(slot, None)
-        else:
-            self._pack_args[slot] = (args_key, n.value, w, keep)
-        return self._store_packed(slot, key, dims, packed, keep, w)
-
-    def _store_packed(self, slot, key, dims, packed, keep, w):
-        entry = _Packed(dims, packed, None)
-        entry._keep = keep
-        entry.weights = w
-        entry.stamp = _stamp(packed)
-        self._packed[slot] = (key, entry)
-        return entry
+        return n.value, w, keep, not (dims.bn or derived[0])
 
     def packed_bwd(self, coarse, entry=None):
         """Transposed fc_0 / fc_1 fragments for the backward kernel, cached with
         the forward blob (rebuilt whenever a parameter changes)."""
         entry = entry or self.packed(coarse)
-        if getattr(entry, "bwd", None) is None:
-            dims = entry.dims
+        if not _hit(entry.bwd, None):
+            dims = entry.dims_as(_lib.FIELD_X3)   # (the backward blob is x3 fragments; the C side reads no precision)
             n = ctypes.c_int64(0)
             _lib.check(_lib.load().avr_field_bwd_packed_floats(ctypes.byref(dims), ctypes.byref(n)),
                        "avr_field_bwd_packed_floats")
             bwd = torch.empty(n.value, device=entry.packed.device, dtype=F32)
             call("avr_field_pack_bwd", ctypes.byref(dims), ctypes.byref(entry.weights), ptr(bwd), stream_of(bwd))
-            entry.bwd, entry.bwd_stamp = bwd, _stamp(bwd)
-        else:
-            _join(entry.bwd_stamp, entry.bwd)
-        return entry.bwd
+            entry.bwd = _Record(None, bwd, None, _stamp(bwd))
+        return entry.bwd.value
 
     def table(self, coarse, sb=0):
         entry = self.packed(coarse)
         lat = self.net.encoder.latent
         key = (sb, _PARAM_GEN[0], lat.data_ptr(), lat._version, tuple(lat.shape))
-        hit = entry.tables.get(sb)
-        if hit is not None and hit[0] == key:
-            _join(hit[3], hit[1])
-            return hit[1]
-        dims = entry.dims
-        L, H, W = lat.shape[1:]
-        latent = lat[sb].detach().to(F32).contiguous()
-        require_device(latent)
-        table = torch.empty(max(n_tables(dims), 1), H * W, dims.d_hidden, device=latent.device, dtype=F32)
-        with _precision(dims, _lib.FIELD_FP32):   # inference: exact fp32 tables, computed once per latent map
+
+        def make():
+            dims = entry.dims_as(_lib.FIELD_FP32)   # inference: exact fp32 tables, computed once per latent map
+            L, H, W = lat.shape[1:]
+            latent = lat[sb].detach().to(F32).contiguous()
+            require_device(latent)
+            table = torch.empty(max(n_tables(dims), 1), H * W, dims.d_hidden, device=latent.device, dtype=F32)
             call("avr_field_latent_table", ctypes.byref(dims), ptr(entry.packed), ptr(latent), H, W, ptr(table),
                  stream_of(table))
-        entry.tables[sb] = (key, table, lat, _stamp(table))  # holding `lat` keeps its address from being reused
-        return table
+            return table
+        return _cached(entry.tables, sb, key, make, keep=lat)   # holding `lat` keeps its address from being reused
 
     def tables_batch(self, coarse, n_scenes, fast=False, bn_fold=True, entry=None):
         """The lin_z tables of scenes 0 .. n_scenes-1 back to back, (n_scenes,
@@ -462,15 +480,11 @@ class FusedField:
         entry = entry or self.packed(coarse, bn_fold)
         lat = self.net.encoder.latent
         key = (n_scenes, bool(fast), _PARAM_GEN[0], lat.data_ptr(), lat._version, tuple(lat.shape))
-        cache = entry.__dict__.setdefault("batch_tables", {})
-        hit = cache.get(bool(fast))
-        if hit is not None and hit[0] == key:
-            _join(hit[3], hit[1])
-            return hit[1]
-        dims = entry.dims
-        L, H, W = lat.shape[1:]
-        out = torch.empty(n_scenes, max(n_tables(dims), 1), H * W, dims.d_hidden, device=lat.device, dtype=F32)
-        with _precision(dims, _lib.FIELD_X3 if fast else _lib.FIELD_FP32):
+
+        def make():
+            dims = entry.dims_as(_lib.FIELD_X3 if fast else _lib.FIELD_FP32)
+            L, H, W = lat.shape[1:]
+            out = torch.empty(n_scenes, max(n_tables(dims), 1), H * W, dims.d_hidden, device=lat.device, dtype=F32)
             if n_scenes <= lat.shape[0]:   # every scene its own map: one launch
                 latent = lat[:n_scenes].detach().to(F32).contiguous()
                 call("avr_field_latent_table_batch", ctypes.byref(dims), ptr(entry.packed), ptr(latent), n_scenes,
@@ -480,42 +494,40 @@ class FusedField:
                     latent = lat[min(sb, lat.shape[0] - 1)].detach().to(F32).contiguous()
                     call("avr_field_latent_table", ctypes.byref(dims), ptr(entry.packed), ptr(latent), H, W,
                          ptr(out[sb]), stream_of(out))
-        cache[bool(fast)] = (key, out, lat, _stamp(out))
-        return out
+            return out
+        return _cached(entry.batch_tables, bool(fast), key, make, keep=lat)
+
+    def _view_sources(self):
+        """The tensors a ViewDesc is read from (a view cache entry holds them: its (ptr, version) key stays sound)."""
+        net = self.net
+        return [net.poses, net.focal, net.c, net.image_shape, net.encoder.latent_scaling]
 
     def view(self, sb=0, ns=1):
         """Source view sb (pose sb; with ns > 1 views per object, focal / principal point of
         object sb // ns, as models.py:796-801 repeat_interleaves them)."""
         net = self.net
-        srcs = [net.poses, net.focal, net.c, net.image_shape, net.encoder.latent_scaling]
+        srcs = self._view_sources()
         key = (sb, ns, _version_key(srcs, gen=False), tuple(net.encoder.latent.shape))
-        hit = self._view_cache.get((sb, ns))
-        if hit is not None and hit[0] == key:
-            return hit[1]
-        pick = lambda t, i=sb: t[min(i, t.shape[0] - 1)] if t.dim() > 1 else t  # noqa: E731
-        v = ViewDesc()
-        v.poses[:] = [float(x) for x in pick(net.poses).reshape(-1)[:12].tolist()]
-        v.focal[:] = [float(x) for x in pick(net.focal, sb // ns).reshape(-1)[:2].tolist()]
-        v.c[:] = [float(x) for x in pick(net.c, sb // ns).reshape(-1)[:2].tolist()]
-        v.image_shape[:] = [float(x) for x in net.image_shape.reshape(-1)[:2].tolist()]
-        v.latent_scaling[:] = [float(x) for x in net.encoder.latent_scaling.reshape(-1)[:2].tolist()]
-        v.latent_h, v.latent_w = int(net.encoder.latent.shape[-2]), int(net.encoder.latent.shape[-1])
-        self._view_cache[(sb, ns)] = (key, v, srcs)  # holding the sources keeps (ptr, version) keys sound
-        return v
+
+        def make():
+            pick = lambda t, i=sb: t[min(i, t.shape[0] - 1)] if t.dim() > 1 else t  # noqa: E731
+            v = ViewDesc()
+            v.poses[:] = [float(x) for x in pick(net.poses).reshape(-1)[:12].tolist()]
+            v.focal[:] = [float(x) for x in pick(net.focal, sb // ns).reshape(-1)[:2].tolist()]
+            v.c[:] = [float(x) for x in pick(net.c, sb // ns).reshape(-1)[:2].tolist()]
+            v.image_shape[:] = [float(x) for x in net.image_shape.reshape(-1)[:2].tolist()]
+            v.latent_scaling[:] = [float(x) for x in net.encoder.latent_scaling.reshape(-1)[:2].tolist()]
+            v.latent_h, v.latent_w = int(net.encoder.latent.shape[-2]), int(net.encoder.latent.shape[-1])
+            return v
+        return _cached(self._view_cache, (sb, ns), key, make, keep=srcs, device=False)
 
     def views(self, idx, ns=1):
         """The ViewDesc array of view(i, ns) for i in the range idx (the multi-scene launches' argument), cached
         under one source-version key (per-view keys for every scene of every launch were host time)."""
-        net = self.net
-        srcs = [net.poses, net.focal, net.c, net.image_shape, net.encoder.latent_scaling]
-        slot = (idx.start, idx.stop, idx.step, ns)
-        key = (_version_key(srcs, gen=False), tuple(net.encoder.latent.shape))
-        hit = self._views_cache.get(slot)
-        if hit is not None and hit[0] == key:
-            return hit[1]
-        arr = (ViewDesc * len(idx))(*[self.view(i, ns) for i in idx])
-        self._views_cache[slot] = (key, arr, srcs)   # holding the sources keeps (ptr, version) keys sound
-        return arr
+        srcs = self._view_sources()
+        key = (_version_key(srcs, gen=False), tuple(self.net.encoder.latent.shape))
+        return _cached(self._views_cache, (idx.start, idx.stop, idx.step, ns), key,
+                       lambda: (ViewDesc * len(idx))(*[self.view(i, ns) for i in idx]), keep=srcs, device=False)
 
     # ----------------------------------------------------------- evaluation
     def forward_rays(self, ro, rd, z, coarse, sb=0):
@@ -528,8 +540,8 @@ class FusedField:
         entry = self.packed(coarse)
         table = self.table(coarse, sb)
         out = torch.empty(R * N, 4, device=z.device, dtype=F32)
-        entry.dims.precision = PRECISIONS[self.precision]
-        call("avr_field_fwd_rays", ctypes.byref(entry.dims), ctypes.byref(self.view(sb)), ptr(entry.packed),
+        dims = entry.dims_as(PRECISIONS[self.precision])
+        call("avr_field_fwd_rays", ctypes.byref(dims), ctypes.byref(self.view(sb)), ptr(entry.packed),
              ptr(table), ptr(ro), ptr(rd), ptr(z), R, N, ptr(out), stream_of(z))
         return out
 
@@ -549,11 +561,10 @@ class FusedField:
             return out
         entry = self.packed(coarse)
         tables = self.tables_batch(coarse, SB)
-        entry.dims.precision = _lib.FIELD_X3
-        for g0 in range(0, SB, _lib.AVR_MAX_SCENES):
-            n = min(_lib.AVR_MAX_SCENES, SB - g0)
+        dims = entry.dims_as(_lib.FIELD_X3)
+        for g0, n in scene_groups(SB):
             views = self.views(range(g0, g0 + n))
-            call("avr_field_fwd_rays_batch", ctypes.byref(entry.dims), views, n, ptr(entry.packed), ptr(tables[g0]),
+            call("avr_field_fwd_rays_batch", ctypes.byref(dims), views, n, ptr(entry.packed), ptr(tables[g0]),
                  ptr(ro[g0]), ptr(rd[g0]), ptr(z[g0 * R]), R, N, ptr(out[g0 * R * N]), stream_of(z))
         return out
 
@@ -569,7 +580,7 @@ class FusedField:
         SB, B, _ = xyz.shape
         mlp = self._mlp(coarse)
         entry = self.packed(coarse)
-        dims = entry.dims
+        dims = entry.dims_as(_lib.FIELD_X3)
         H, nb, cl = dims.d_hidden, dims.n_blocks, mlp.combine_layer
         dev = xyz.device
         p = xyz.to(F32).repeat_interleave(NS, 0).contiguous()              # (SB*NS, B, 3), views of an object adjacent
@@ -579,18 +590,15 @@ class FusedField:
         tables = self.tables_batch(coarse, K)
         h = torch.empty(K * B, H, device=dev, dtype=F32)
         out = torch.empty(SB, B, 4, device=dev, dtype=F32)
-        with _precision(dims, _lib.FIELD_X3):
-            for g0 in range(0, K, _lib.AVR_MAX_SCENES):
-                n = min(_lib.AVR_MAX_SCENES, K - g0)
-                views = self.views(range(g0, g0 + n), NS)
-                call("avr_field_fwd_points_split", ctypes.byref(entry.dims), views, n, ptr(entry.packed),
-                     ptr(tables[g0]), ptr(p[g0]), ptr(v[g0]), B, 0, cl, None, ptr(h[g0 * B]), None, stream_of(p))
-            hc = combine_interleaved(h, (NS, B), mlp.combine_type).reshape(SB * B, H).contiguous()
-            for g0 in range(0, SB, _lib.AVR_MAX_SCENES):
-                n = min(_lib.AVR_MAX_SCENES, SB - g0)
-                views = self.views(range(g0 * NS, (g0 + n) * NS, NS), NS)
-                call("avr_field_fwd_points_split", ctypes.byref(entry.dims), views, n, ptr(entry.packed),
-                     ptr(tables[0]), None, None, B, cl, nb, ptr(hc[g0 * B]), None, ptr(out[g0]), stream_of(p))
+        for g0, n in scene_groups(K):
+            views = self.views(range(g0, g0 + n), NS)
+            call("avr_field_fwd_points_split", ctypes.byref(dims), views, n, ptr(entry.packed),
+                 ptr(tables[g0]), ptr(p[g0]), ptr(v[g0]), B, 0, cl, None, ptr(h[g0 * B]), None, stream_of(p))
+        hc = combine_interleaved(h, (NS, B), mlp.combine_type).reshape(SB * B, H).contiguous()
+        for g0, n in scene_groups(SB):
+            views = self.views(range(g0 * NS, (g0 + n) * NS, NS), NS)
+            call("avr_field_fwd_points_split", ctypes.byref(dims), views, n, ptr(entry.packed),
+                 ptr(tables[0]), None, None, B, cl, nb, ptr(hc[g0 * B]), None, ptr(out[g0]), stream_of(p))
         return out
 
     def forward_points(self, xyz, viewdirs, coarse):
@@ -610,20 +618,19 @@ class FusedField:
             v = viewdirs.reshape(SB, B, 3).to(F32).contiguous()
             require_device(p, v)
             tables = self.tables_batch(coarse, SB)
-            entry.dims.precision = _lib.FIELD_X3
-            for g0 in range(0, SB, _lib.AVR_MAX_SCENES):
-                n = min(_lib.AVR_MAX_SCENES, SB - g0)
+            dims = entry.dims_as(_lib.FIELD_X3)
+            for g0, n in scene_groups(SB):
                 views = self.views(range(g0, g0 + n))
-                call("avr_field_fwd_points_batch", ctypes.byref(entry.dims), views, n, ptr(entry.packed),
+                call("avr_field_fwd_points_batch", ctypes.byref(dims), views, n, ptr(entry.packed),
                      ptr(tables[g0]), ptr(p[g0]), ptr(v[g0]), B, ptr(out[g0]), stream_of(p))
             return out
+        dims = entry.dims_as(PRECISIONS[self.precision])
         for sb in range(SB):
             p = xyz[sb].to(F32).contiguous()
             v = viewdirs.reshape(SB, B, 3)[sb].to(F32).contiguous()
             require_device(p, v)
             table = self.table(coarse, sb)
-            entry.dims.precision = PRECISIONS[self.precision]
-            call("avr_field_fwd_points", ctypes.byref(entry.dims), ctypes.byref(self.view(sb)), ptr(entry.packed),
+            call("avr_field_fwd_points", ctypes.byref(dims), ctypes.byref(self.view(sb)), ptr(entry.packed),
                  ptr(table), ptr(p), ptr(v), B, ptr(out[sb]), stream_of(p))
         return out
 
@@ -632,39 +639,30 @@ class FusedField:
         """The rf(xyz, viewdirs, coarse) protocol with autograd: HIP forward that
         keeps every GEMM input, HIP backward through the ResnetFC, weight
         gradients as GEMMs over the samples (see _FieldTrain)."""
-        mlp = self._mlp(coarse)
-        names = train_param_names(mlp)
-        named, _, _ = self._state(mlp)
-        params = [named[n] for n in names]
-        return _FieldTrain.apply(self, coarse, names, xyz, viewdirs, self.net.encoder.latent, *params)
+        return train_common.forward_train(self, xyz, viewdirs, coarse, _FieldTrain, train_param_names)
 
 
 def _feat_grad(fused, entry, bwd, Gz, P, Mt):
     """The looked-up latent features' gradient sum_b Gz[b] . W_z[b] (the point / latent gradients' input):
     avr_bn_layer_run's lin_z[b]^T layers from the backward blob (x3, ABI 14), one launch per layer adding the
     previous layers' sum in its epilogue, where they apply (d_latent == d_hidden, ReLU, 64..512 wide); else
-    fp32 library GEMMs (avr.ops.sum_of_products)."""
-    from .bn_train import _layer, _partial, _run
-    from .ops import sum_of_products
-    dims = entry.dims
+    fp32 library GEMMs (avr.ops.sum_of_products). entry: anything holding the blob's dims (an x3 copy is made)."""
+    from .bn_train import _layer, _partial, _run   # (avr.bn_train imports this module)
+    dims = entry.dims.with_precision(_lib.FIELD_X3)
     H, nz = dims.d_hidden, dims.n_lin_z
     if not (dims.d_latent == H and H in (64, 128, 256, 512) and not dims.spade and not dims.bn
             and not dims.beta > 0 and Mt > 0 and all(g.is_contiguous() for g in Gz)):
-        return sum_of_products([(Gz[b], P[f"lin_z.{b}.weight"].detach()) for b in range(nz)])
+        return ops.sum_of_products([(Gz[b], P[f"lin_z.{b}.weight"].detach()) for b in range(nz)])
     dev = Gz[0].device
     part = _partial(Mt, H, dev)
     stream = stream_of(Gz[0])
     prev = None
-    saved, dims.precision = dims.precision, _lib.FIELD_X3
-    try:
-        for b in range(nz):
-            out = torch.empty(Mt, H, device=dev, dtype=F32)
-            _run(dims, _layer(n_rows=Mt, mode=_lib.BN_BWD, prologue=_lib.BN_PLAIN, in_dim=H, in_valid=H, src=Gz[b],
-                              ld_src=H, blob=bwd, layer=_lib.BN_LAYER_LIN_Z_T + b, add1=prev, out=out, partial=part),
-                 stream)
-            prev = out
-    finally:
-        dims.precision = saved
+    for b in range(nz):
+        out = torch.empty(Mt, H, device=dev, dtype=F32)
+        _run(dims, _layer(n_rows=Mt, mode=_lib.BN_BWD, prologue=_lib.BN_PLAIN, in_dim=H, in_valid=H, src=Gz[b],
+                          ld_src=H, blob=bwd, layer=_lib.BN_LAYER_LIN_Z_T + b, add1=prev, out=out, partial=part),
+             stream)
+        prev = out
     return prev
 
 
@@ -678,6 +676,109 @@ def train_param_names(mlp):
     return names
 
 
+def _bwd_chain(dims, entry, bwd, masks, B, Mt, out, grad_out, act):
+    """avr_field_bwd per group of scenes: the gradient at every layer output, (layers, Mt, d_hidden), and each
+    layer's max |gradient| as int32 float bits."""
+    H, n_l = dims.d_hidden, 2 * dims.n_blocks + 1
+    G = torch.empty(n_l, Mt, H, device=out.device, dtype=F32)
+    g_max = torch.zeros(n_l, device=out.device, dtype=torch.int32)
+    for g0, n, mask in masks:
+        call("avr_field_bwd", ctypes.byref(dims), ptr(entry.packed), ptr(bwd), n, B, ptr(out[g0]),
+             ptr(grad_out[g0]), ptr(mask), ctypes.c_void_p(act.data_ptr() + g0 * B * H * 4), Mt,
+             ctypes.c_void_p(G.data_ptr() + g0 * B * H * 4), Mt, ptr(g_max), stream_of(G))
+    return G, g_max
+
+
+def _weight_grads(dims, Mt, G, g_max, act, act_max, lat_feat, lat_max, zf, d4, d4_max):
+    """Every weight and bias gradient by parameter name, from one batched avr_weight_grads launch. Its layers are
+    addressed by offset into the buffers _FieldTrain allocated (row strides H, d_latent, zs, 4; 16-B aligned by
+    construction): the fc layers (G_k, act_k), lin_z[b] (the gradient at block b's input, the interpolated
+    latent), lin_in (the gradient at the first block's input, z_feature with its max in act_max[n_l]), lin_out
+    (d4, the last block's output) -- no per-layer views or checks."""
+    H, nb, nz, d_latent = dims.d_hidden, dims.n_blocks, dims.n_lin_z, dims.d_latent
+    Gp, Ap, gmp, amp, lay = G.data_ptr(), act.data_ptr(), g_max.data_ptr(), act_max.data_ptr(), Mt * H * 4
+    specs = [(Gp + k * lay, H, Ap + k * lay, H, H, H, gmp + 4 * k, amp + 4 * k, True, None, None, None, 0)
+             for k in range(2 * nb)]
+    for b in range(nz):
+        k = 2 * b - 1 if b > 0 else 2 * nb
+        specs.append((Gp + k * lay, H, lat_feat.data_ptr(), d_latent, H, d_latent, gmp + 4 * k,
+                      lat_max.data_ptr(), False, None, None, None, 0))
+    specs.append((Gp + 2 * nb * lay, H, zf.data_ptr(), zf.shape[1], H, zf.shape[1], gmp + 8 * nb,
+                  amp + 4 * (2 * nb + 1), True, None, None, None, 0))
+    specs.append((d4.data_ptr(), 4, Ap + 2 * nb * lay, H, 4, H, d4_max.data_ptr(), amp + 8 * nb, True, None, None,
+                  None, 0))
+    res = ops.weight_grads_specs(specs, Mt, G.device, stream_of(G))
+    grads = {"lin_out.weight": res[-1][0], "lin_out.bias": res[-1][1]}
+    res = res[:-1]
+    for b in range(nb):
+        grads[f"blocks.{b}.fc_0.weight"], grads[f"blocks.{b}.fc_0.bias"] = res[2 * b]
+        grads[f"blocks.{b}.fc_1.weight"], grads[f"blocks.{b}.fc_1.bias"] = res[2 * b + 1]
+    for b in range(nz):
+        grads[f"lin_z.{b}.weight"] = res[2 * nb + b][0]
+        # lin_z[b]'s output gradient is the gradient at block b's input
+        grads[f"lin_z.{b}.bias"] = res[2 * b - 1][1] if b > 0 else res[-1][1]
+    w_in, b_in = res[-1]
+    grads["lin_in.weight"], grads["lin_in.bias"] = w_in[:, :dims.d_in].contiguous(), b_in
+    return grads
+
+
+def _lookup_point_grad(fused, entry, bwd, tables, latent, p, B, Gz, P):
+    """d loss / d points through the latent lookup, (SB * B, 3), on HIP. From the forward's per-texel tables:
+    sum_b Gz[b] . lin_z[b](interp(latent, p)) = sum_b Gz[b] . interp(table_b, p), the corner differences of the
+    tables against each Gz row (ABI 15), no d_hidden x d_latent product per point for the feature gradient. Where
+    that does not apply (or AVR_POINT_GRAD_VIA_FEATURES=1): the features' gradient through the lookup's adjoint."""
+    dims = entry.dims
+    H, nz = dims.d_hidden, dims.n_lin_z
+    SB = p.shape[0]
+    d_look = torch.empty(SB * B, 3, device=p.device, dtype=F32)
+    if (not dims.spade and nz <= _lib.AVR_LOOKUP_GRAD_TERMS and tables.shape[0] == SB
+            and os.environ.get("AVR_POINT_GRAD_VIA_FEATURES") != "1"):
+        ld = Gz[0].stride(0)
+        assert all(g.stride(0) == ld and g.stride(1) == 1 for g in Gz)
+        gptr = [g.data_ptr() for g in Gz]
+        for g0, n in scene_groups(SB):
+            gr = (ctypes.c_void_p * nz)(*[g + g0 * B * ld * 4 for g in gptr])
+            call("avr_latent_tables_grad_points", fused.views(range(g0, g0 + n)), n, ptr(tables[g0]),
+                 tables.stride(0), tables.stride(1), nz, H, ptr(p[g0]), B, gr, ld, ptr(d_look[g0 * B]),
+                 stream_of(d_look))
+        return d_look
+    g_feat = _feat_grad(fused, entry, bwd, Gz, P, SB * B)
+    hwc = fused.latent_hwc_all(latent)
+    for g0, n in scene_groups(SB):
+        call("avr_latent_features_grad_points", fused.views(range(g0, g0 + n)), n, ptr(hwc[g0]), dims.d_latent,
+             ptr(p[g0]), B, ptr(g_feat[g0 * B]), ptr(d_look[g0 * B]), stream_of(d_look))
+    return d_look
+
+
+def _point_grad_hip(fused, entry, bwd, tables, xyz, viewdirs, latent, p, G_in, Gz, P):
+    """d loss / d xyz for the points alone (the adaptive renderer's band, fixed latent) on HIP: the lookup's part
+    (_lookup_point_grad), then z_feature's added to it (ABI 16): d loss / d z_feature = G_in W_in (its
+    positional-encoded columns only), then the encoding's and the rotation's adjoint per point in one launch.
+    With stop_encoder_grad the looked-up latent is detached (models.py:810-811): z_feature's part alone.
+    AVR_POINT_ZF_VIA_AUTOGRAD=1: torch autograd of z_features instead, the round-5 path, for A/B."""
+    net, dims = fused.net, entry.dims
+    SB, B, _ = xyz.shape
+    d_look = None
+    if not net.stop_encoder_grad:
+        with torch.no_grad():
+            d_look = _lookup_point_grad(fused, entry, bwd, tables, latent, p, B, Gz, P)
+    if os.environ.get("AVR_POINT_ZF_VIA_AUTOGRAD") == "1":
+        with torch.enable_grad():
+            x = xyz.detach().requires_grad_(True)
+            zft = net.z_features(x, viewdirs.detach())
+            d_z, = torch.autograd.grad(zft, x, G_in @ P["lin_in.weight"].detach())
+        return (d_z if d_look is None else d_look.reshape(SB, B, 3) + d_z).to(xyz.dtype)
+    with torch.no_grad():
+        d_zf = G_in @ P["lin_in.weight"].detach()[:, :3 + 6 * dims.num_freqs]
+        if d_look is None:
+            d_look = torch.empty(SB * B, 3, device=xyz.device, dtype=F32)
+        for g0, n in scene_groups(SB):
+            call("avr_zfeature_grad_points", fused.views(range(g0, g0 + n)), n, ptr(p[g0]), B, ptr(d_zf[g0 * B]),
+                 d_zf.stride(0), dims.num_freqs, dims.freq_factor, int(not net.stop_encoder_grad),
+                 ptr(d_look[g0 * B]), stream_of(d_look))
+    return d_look.reshape(SB, B, 3).to(xyz.dtype)
+
+
 class _FieldTrain(torch.autograd.Function):
     """Autograd of NewPixelNeRFNet.forward (models.py:739-863) for train.py's
     loss.backward() (train.py:108-114).
@@ -687,19 +788,20 @@ class _FieldTrain(torch.autograd.Function):
     layer's running max) into one (layers, SB * B, d_hidden) buffer.
     backward: avr_field_bwd runs the input-gradient chain per scene (lin_out^T,
     then fc_1^T / fc_0^T per block with the relu masks, x3 MFMA) and writes the
-    gradient at every layer output; avr_weight_grads then forms every weight
-    and bias gradient in one batched split-K x3 GEMM over all samples
-    (fc_0 / fc_1 against the saved inputs, lin_z against the interpolated latent
-    (grid_sample, models.py:266-273), lin_in against the positional-encoded
-    input). The latent map gets the grid_sample adjoint of sum_b G_z[b] W_z[b]
-    when it requires grad."""
+    gradient at every layer output (_bwd_chain); avr_weight_grads then forms every
+    weight and bias gradient in one batched split-K x3 GEMM over all samples
+    (_weight_grads: fc_0 / fc_1 against the saved inputs, lin_z against the
+    interpolated latent (grid_sample, models.py:266-273), lin_in against the
+    positional-encoded input). The points get their gradient on HIP when they alone
+    want one (_point_grad_hip); otherwise the inputs' gradients go through torch's
+    input functions (input_grads_via_autograd): the latent map gets the grid_sample
+    adjoint of sum_b G_z[b] W_z[b] when it requires grad."""
 
     @staticmethod
     def forward(ctx, fused, coarse, names, xyz, viewdirs, latent, *params):
         SB, B, _ = xyz.shape
         entry = fused.packed(coarse)
-        dims = entry.dims
-        dims.precision = _lib.FIELD_X3
+        dims = entry.dims_as(_lib.FIELD_X3)
         H, nb = dims.d_hidden, dims.n_blocks
         n_l, Mt = 2 * nb + 1, SB * B
         dev = xyz.device
@@ -713,8 +815,7 @@ class _FieldTrain(torch.autograd.Function):
         require_device(p, v)
         tables = fused.tables_batch(coarse, SB, fast=True, entry=entry)
         masks = []
-        for g0 in range(0, SB, _lib.AVR_MAX_SCENES):     # one launch per group of scenes
-            n = min(_lib.AVR_MAX_SCENES, SB - g0)
+        for g0, n in scene_groups(SB):     # one launch per group of scenes
             act_n, mask_n = ctypes.c_int64(0), ctypes.c_int64(0)
             _lib.check(_lib.load().avr_field_train_sizes(ctypes.byref(dims), n, B, ctypes.byref(act_n),
                                                          ctypes.byref(mask_n)), "avr_field_train_sizes")
@@ -725,7 +826,6 @@ class _FieldTrain(torch.autograd.Function):
                  ptr(mask), ptr(act_max), ctypes.c_void_p(zf.data_ptr() + g0 * B * zs * 4), zs,
                  ctypes.c_void_p(act_max.data_ptr() + 4 * n_l), stream_of(p))
             masks.append((g0, n, mask))
-        entry.dims.precision = PRECISIONS[fused.precision]
         ctx.fused, ctx.coarse, ctx.names, ctx.entry = fused, coarse, names, entry
         ctx.act, ctx.act_max, ctx.masks, ctx.zf = act, act_max, masks, zf
         ctx.tables = tables
@@ -734,163 +834,41 @@ class _FieldTrain(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, grad_out):
-        from .ops import latent_features, lin_out_act_bwd, weight_grads_specs
         xyz, viewdirs, latent, out, *params = ctx.saved_tensors
         fused, entry, names = ctx.fused, ctx.entry, ctx.names
         net = fused.net
         P = dict(zip(names, params))
-        dims = entry.dims
-        H, nb, nz = dims.d_hidden, dims.n_blocks, dims.n_lin_z
+        dims = entry.dims_as(_lib.FIELD_X3)
+        nb, nz = dims.n_blocks, dims.n_lin_z
         SB, B, _ = xyz.shape
-        n_l, Mt = 2 * nb + 1, SB * B
+        Mt = SB * B
+        want_xyz = ctx.needs_input_grad[3]
         want_latent = ctx.needs_input_grad[5] and not net.stop_encoder_grad
         if B == 0:
             zeros = tuple(torch.zeros_like(p) if ctx.needs_input_grad[6 + i] else None for i, p in enumerate(params))
-            return (None, None, None, torch.zeros_like(xyz) if ctx.needs_input_grad[3] else None, None,
+            return (None, None, None, torch.zeros_like(xyz) if want_xyz else None, None,
                     torch.zeros_like(latent) if want_latent else None) + zeros
-        dev = xyz.device
-        dims.precision = _lib.FIELD_X3
         bwd = fused.packed_bwd(ctx.coarse, entry)
         grad_out = grad_out.to(F32).contiguous()
-        G = torch.empty(n_l, Mt, H, device=dev, dtype=F32)
-        g_max = torch.zeros(n_l, device=dev, dtype=torch.int32)
-        act = ctx.act
-        for g0, n, mask in ctx.masks:
-            call("avr_field_bwd", ctypes.byref(dims), ptr(entry.packed), ptr(bwd), n, B, ptr(out[g0]),
-                 ptr(grad_out[g0]), ptr(mask), ctypes.c_void_p(act.data_ptr() + g0 * B * H * 4), Mt,
-                 ctypes.c_void_p(G.data_ptr() + g0 * B * H * 4), Mt, ptr(g_max), stream_of(G))
-        entry.dims.precision = PRECISIONS[fused.precision]
-        act_max, zf = ctx.act_max, ctx.zf
+        act, act_max, zf = ctx.act, ctx.act_max, ctx.zf
+        G, g_max = _bwd_chain(dims, entry, bwd, ctx.masks, B, Mt, out, grad_out, act)
         ctx.act = ctx.act_max = ctx.masks = ctx.zf = None
-        # MLP inputs the lin_z / lin_in gradients contract against: the latent
-        # features (avr_latent_features, row-major) and z_feature (the training forward
-        # stored it, padded to 16 B, with its max in act_max[n_l])
-        d_in = dims.d_in
+        # MLP inputs the lin_z / lin_in gradients contract against: the latent features (row-major) and z_feature
+        # (the training forward stored it, padded to 16 B)
         p = xyz.detach().to(F32).contiguous()
         with torch.no_grad():
-            lat_feat = torch.empty(Mt, net.d_latent, device=dev, dtype=F32)
-            if SB <= latent.shape[0]:   # every scene its own map: one launch per AVR_MAX_SCENES scenes
-                hwc = fused.latent_hwc_all(latent)
-                for g0 in range(0, SB, _lib.AVR_MAX_SCENES):
-                    n = min(_lib.AVR_MAX_SCENES, SB - g0)
-                    views = fused.views(range(g0, g0 + n))
-                    call("avr_latent_features_batch", views, n, ptr(hwc[g0]), net.d_latent, ptr(p[g0]), B,
-                         ptr(lat_feat[g0 * B]), stream_of(lat_feat))
-            else:
-                for sb in range(SB):
-                    s = min(sb, latent.shape[0] - 1)
-                    latent_features(fused.view(sb), latent[s], xyz[sb], out=lat_feat[sb * B:(sb + 1) * B],
-                                    hwc=fused.latent_hwc(latent, s))
+            lat_feat = lookup_features(fused, latent, p, SB, B)
         lat_max = fused.latent_max_bits(latent)   # |interpolated latent| <= max |latent| (convex blend)
-        zf_max = act_max[n_l:n_l + 1]
         Gz = [G[2 * b - 1] if b > 0 else G[2 * nb] for b in range(nz)]
         # lin_out (4 outputs): d out through sigmoid / relu (torch: g * (1 - y) * y, g * (y > 0)), with its max
-        d4, d4_max = lin_out_act_bwd(grad_out, out)
-        # the layers of the batched weight-gradient launch addressed by offset into the buffers this Function
-        # allocated (row strides H, d_latent, zs, 4; 16-B aligned by construction): the fc layers (G_k, act_k),
-        # lin_z[b] (the gradient at block b's input, the interpolated latent), lin_in (the gradient at the first
-        # block's input, z_feature), lin_out (d4, the last block's output) -- no per-layer views or checks
-        Gp, Ap, gmp, amp, lay = G.data_ptr(), act.data_ptr(), g_max.data_ptr(), act_max.data_ptr(), Mt * H * 4
-        specs = [(Gp + k * lay, H, Ap + k * lay, H, H, H, gmp + 4 * k, amp + 4 * k, True, None, None, None, 0)
-                 for k in range(2 * nb)]
-        for b in range(nz):
-            k = 2 * b - 1 if b > 0 else 2 * nb
-            specs.append((Gp + k * lay, H, lat_feat.data_ptr(), net.d_latent, H, net.d_latent, gmp + 4 * k,
-                          lat_max.data_ptr(), False, None, None, None, 0))
-        specs.append((Gp + 2 * nb * lay, H, zf.data_ptr(), zf.shape[1], H, zf.shape[1], gmp + 8 * nb,
-                      zf_max.data_ptr(), True, None, None, None, 0))
-        specs.append((d4.data_ptr(), 4, Ap + 2 * nb * lay, H, 4, H, d4_max.data_ptr(), amp + 8 * nb, True, None, None,
-                      None, 0))
-        res = weight_grads_specs(specs, Mt, dev, stream_of(G))
-        grads = {"lin_out.weight": res[-1][0], "lin_out.bias": res[-1][1]}
-        res = res[:-1]
-        for b in range(nb):
-            grads[f"blocks.{b}.fc_0.weight"], grads[f"blocks.{b}.fc_0.bias"] = res[2 * b]
-            grads[f"blocks.{b}.fc_1.weight"], grads[f"blocks.{b}.fc_1.bias"] = res[2 * b + 1]
-        for b in range(nz):
-            grads[f"lin_z.{b}.weight"] = res[2 * nb + b][0]
-            # lin_z[b]'s output gradient is the gradient at block b's input
-            grads[f"lin_z.{b}.bias"] = res[2 * b - 1][1] if b > 0 else res[-1][1]
-        w_in, b_in = res[-1]
-        grads["lin_in.weight"], grads["lin_in.bias"] = w_in[:, :d_in].contiguous(), b_in
-        # the gradient at the MLP inputs, sent through the (cheap) torch input
-        # functions: the latent map via the grid_sample adjoint, the points via
-        # PE / rotation / projection (the adaptive renderer's band points)
+        d4, d4_max = ops.lin_out_act_bwd(grad_out, out)
+        grads = _weight_grads(dims, Mt, G, g_max, act, act_max, lat_feat, lat_max, zf, d4, d4_max)
         d_latent = d_xyz = None
-        want_xyz = ctx.needs_input_grad[3]
         if want_xyz and not want_latent and (net.stop_encoder_grad or (nz > 0 and SB <= latent.shape[0])):
-            # the points alone (the adaptive renderer's band, fixed latent): the lookup's adjoint on HIP
-            # (avr_latent_tables_grad_points / avr_latent_features_grad_points), then z_feature's. With
-            # stop_encoder_grad the looked-up latent is detached (models.py:810-811), so no gradient reaches the
-            # points through the lookup: z_feature's part alone.
-            d_look = None
-            if not net.stop_encoder_grad:
-                with torch.no_grad():
-                    d_look = torch.empty(Mt, 3, device=dev, dtype=F32)
-                    tabs = ctx.tables
-                    via_tables = (not dims.spade and nz <= _lib.AVR_LOOKUP_GRAD_TERMS and tabs.shape[0] == SB
-                                  and os.environ.get("AVR_POINT_GRAD_VIA_FEATURES") != "1")
-                    if via_tables:
-                        # sum_b Gz[b] . lin_z[b](interp(latent, p)) = sum_b Gz[b] . interp(table_b, p): the corner
-                        # differences of the forward's per-texel tables against each Gz row (ABI 15), no
-                        # d_hidden x d_latent product per point for the feature gradient
-                        ld = Gz[0].stride(0)
-                        assert all(g.stride(0) == ld and g.stride(1) == 1 for g in Gz)
-                        gptr = [g.data_ptr() for g in Gz]
-                        for g0 in range(0, SB, _lib.AVR_MAX_SCENES):
-                            n = min(_lib.AVR_MAX_SCENES, SB - g0)
-                            views = fused.views(range(g0, g0 + n))
-                            gr = (ctypes.c_void_p * nz)(*[g + g0 * B * ld * 4 for g in gptr])
-                            call("avr_latent_tables_grad_points", views, n, ptr(tabs[g0]), tabs.stride(0),
-                                 tabs.stride(1), nz, H, ptr(p[g0]), B, gr, ld, ptr(d_look[g0 * B]),
-                                 stream_of(d_look))
-                    else:
-                        g_feat = _feat_grad(fused, entry, bwd, Gz, P, Mt)
-                        hwc = fused.latent_hwc_all(latent)
-                        for g0 in range(0, SB, _lib.AVR_MAX_SCENES):
-                            n = min(_lib.AVR_MAX_SCENES, SB - g0)
-                            views = fused.views(range(g0, g0 + n))
-                            call("avr_latent_features_grad_points", views, n, ptr(hwc[g0]), net.d_latent,
-                                 ptr(p[g0]), B, ptr(g_feat[g0 * B]), ptr(d_look[g0 * B]), stream_of(d_look))
-            # z_feature's part (ABI 16): d loss / d z_feature = G_in W_in (its positional-encoded columns only), then
-            # the encoding's and the rotation's adjoint per point in one launch, added to the lookup's part
-            # (AVR_POINT_ZF_VIA_AUTOGRAD=1: torch autograd of z_features instead, the round-5 path, for A/B)
-            n_pe = 3 + 6 * dims.num_freqs
-            if os.environ.get("AVR_POINT_ZF_VIA_AUTOGRAD") == "1":
-                with torch.enable_grad():
-                    x = xyz.detach().requires_grad_(True)
-                    zft = net.z_features(x, viewdirs.detach())
-                    d_z, = torch.autograd.grad(zft, x, G[2 * nb] @ P["lin_in.weight"].detach())
-                d_xyz = (d_z if d_look is None else d_look.reshape(SB, B, 3) + d_z).to(xyz.dtype)
-            else:
-                with torch.no_grad():
-                    d_zf = G[2 * nb] @ P["lin_in.weight"].detach()[:, :n_pe]
-                    if d_look is None:
-                        d_look = torch.empty(Mt, 3, device=dev, dtype=F32)
-                    for g0 in range(0, SB, _lib.AVR_MAX_SCENES):
-                        n = min(_lib.AVR_MAX_SCENES, SB - g0)
-                        views = fused.views(range(g0, g0 + n))
-                        call("avr_zfeature_grad_points", views, n, ptr(p[g0]), B, ptr(d_zf[g0 * B]), d_zf.stride(0),
-                             dims.num_freqs, dims.freq_factor, int(not net.stop_encoder_grad), ptr(d_look[g0 * B]),
-                             stream_of(d_look))
-                d_xyz = d_look.reshape(SB, B, 3).to(xyz.dtype)
+            d_xyz = _point_grad_hip(fused, entry, bwd, ctx.tables, xyz, viewdirs, latent, p, G[2 * nb], Gz, P)
         elif want_latent or want_xyz:
-            with torch.enable_grad():
-                lat = latent.detach().requires_grad_(want_latent)
-                x = xyz.detach().requires_grad_(want_xyz)
-                feat, zft = net.mlp_inputs(x, viewdirs.detach(), latent=lat)
-                outs, grads_out = [], []
-                if nz > 0:
-                    outs.append(feat)
-                    grads_out.append(_feat_grad(fused, entry, bwd, Gz, P, Mt))
-                if want_xyz:
-                    outs.append(zft)
-                    grads_out.append(G[2 * nb] @ P["lin_in.weight"].detach())
-                wrt = ([lat] if want_latent else []) + ([x] if want_xyz else [])
-                res_in = torch.autograd.grad(outs, wrt, grads_out, allow_unused=True)
-            if want_latent:
-                d_latent = res_in[0] if res_in[0] is not None else torch.zeros_like(latent)
-            if want_xyz:
-                d_xyz = res_in[-1] if res_in[-1] is not None else torch.zeros_like(xyz)
+            g_feat = _feat_grad(fused, entry, bwd, Gz, P, Mt) if nz > 0 else None
+            g_zf = G[2 * nb] @ P["lin_in.weight"].detach() if want_xyz else None
+            d_latent, d_xyz = input_grads_via_autograd(net, xyz, viewdirs, latent, want_latent, want_xyz, g_feat, g_zf)
         return (None, None, None, d_xyz, None, d_latent) + tuple(
             grads[n] if ctx.needs_input_grad[6 + i] else None for i, n in enumerate(names))

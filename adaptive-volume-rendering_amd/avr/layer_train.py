@@ -21,12 +21,14 @@ statistics: the operand is relu(x), the backward's mask [pre > 0]) with the elem
             staging), scale_z's against (g * X) rows; the latent / point gradients through the input functions
             as in avr.field._FieldTrain (the features' gradient on the lin_z^T layers where they apply).
 """
-import ctypes
-
 import torch
 
-from . import _lib
-from ._lib import call, ptr, stream_of
+from . import _lib, ops
+from ._lib import stream_of
+from .field import _feat_grad, fused_eligible, softplus_beta, train_param_names, uses_bn
+from .models import combine_interleaved
+from .train_common import (forward_train, gather_rows as _gather, input_grads_via_autograd, lin_z_epilogue,
+                           padded_z_features)
 
 F32 = torch.float32
 
@@ -35,7 +37,6 @@ def layer_train_eligible(net):
     """A NewPixelNeRFNet this path trains: what the fused field runs for inference (avr.field.fused_eligible, with
     NS > 1 its multiview form), ReLU, no BatchNorm, and use_spade or NS > 1 source views (the other nets train on
     the fused kernels, avr.field._FieldTrain), d_latent a multiple of 64 up to 512 (x3 tables)."""
-    from .field import fused_eligible, softplus_beta, uses_bn
     try:
         mlps = [net.mlp_coarse] + ([net.mlp_fine] if net.mlp_fine is not None else [])
         ns = net.num_views_per_obj
@@ -51,7 +52,6 @@ def layer_train_eligible(net):
 
 
 def train_param_names_layers(mlp):
-    from .field import train_param_names
     names = train_param_names(mlp)
     if getattr(mlp, "use_spade", False):
         for b in range(min(mlp.combine_layer, mlp.n_blocks)):
@@ -61,23 +61,7 @@ def train_param_names_layers(mlp):
 
 def forward_train_layers(fused, xyz, viewdirs, coarse):
     """The rf(xyz, viewdirs, coarse) protocol on this path (autograd when enabled)."""
-    mlp = fused._mlp(coarse)
-    names = train_param_names_layers(mlp)
-    named, _, _ = fused._state(mlp)
-    return _FieldTrainLayers.apply(fused, coarse, names, xyz, viewdirs, fused.net.encoder.latent,
-                                   *[named[n] for n in names])
-
-
-def _gather(fused, tab, K, NS, p, B, C):
-    """Bilinear blends (avr_latent_features' lookup and order) of the (K, H*W, C) per-texel rows `tab` at the
-    points p (K, B, 3), scene k seen from source view k (object k // NS) -> (K * B, C)."""
-    out = torch.empty(K * B, C, device=p.device, dtype=F32)
-    for g0 in range(0, K, _lib.AVR_MAX_SCENES):
-        n = min(_lib.AVR_MAX_SCENES, K - g0)
-        views = fused.views(range(g0, g0 + n), NS)
-        call("avr_latent_features_batch", views, n, ptr(tab[g0]), C, ptr(p[g0]), B, ptr(out[g0 * B]),
-             stream_of(out))
-    return out
+    return forward_train(fused, xyz, viewdirs, coarse, _FieldTrainLayers, train_param_names_layers)
 
 
 class _Ident:
@@ -94,14 +78,12 @@ class _FieldTrainLayers(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, fused, coarse, names, xyz, viewdirs, latent, *params):
-        from .bn_train import _layer, _partial, _run
-        from .models import combine_interleaved
-        from .ops import lin_out_rows
+        from .bn_train import _layer, _partial, _run   # (per call: scripts/layer_train_debug.py wraps them there)
         net = fused.net
         mlp = fused._mlp(coarse)
         P = dict(zip(names, params))
         entry = fused.packed(coarse)
-        dims = entry.dims
+        dims = entry.dims.with_precision(_lib.FIELD_X3)
         H, nb, nz = dims.d_hidden, dims.n_blocks, dims.n_lin_z
         spade = bool(dims.spade)
         NS = net.num_views_per_obj
@@ -113,23 +95,14 @@ class _FieldTrainLayers(torch.autograd.Function):
         stream = stream_of(xyz)
         with torch.no_grad():
             p = xyz.detach().to(F32).repeat_interleave(NS, 0).contiguous()      # (object, view) rows
-            zf = net.z_features(xyz.detach(), viewdirs.detach()).to(F32)          # (M1, d_in)
-            d_in = zf.shape[1]
-            zs = d_in + (-d_in) % 4
-            zfp = torch.zeros(M1, zs, device=dev, dtype=F32)
-            zfp[:, :d_in] = zf
+            zfp, d_in, zs = padded_z_features(net, xyz, viewdirs)                 # (M1, zs)
             tables = fused.tables_batch(coarse, K, fast=True)                     # (K, n_tables, HW, H)
             # without use_spade, X'[b] = X[b] + T_b: the T rows gathered in the epilogue of the layer producing X[b]
             # (avr_bn_layer's lin_z_table, as avr.bn_train; nz <= combine_layer, so X[b] is X'[b] and no T row is
             # stored); use_spade's product, or more scenes than one launch takes, gathers them here
             zk = not spade and 0 < nz and K <= _lib.AVR_MAX_SCENES
             views = fused.views(range(K), NS) if zk else None
-
-            def lin_z(b):
-                if not zk or b >= nz:
-                    return {}
-                return dict(lin_z_table=tables[0, b], lin_z_scene_stride=tables.stride(0), xyz=p,
-                            views=ctypes.addressof(views), n_views=K, rows_per_scene=B)
+            lin_z = lambda b: lin_z_epilogue(tables, b, nz, p, views, K, B) if zk else {}   # noqa: E731
             T = [] if zk else [_gather(fused, tables[:, b].contiguous(), K, NS, p, B, H) for b in range(nz)]
             S = [_gather(fused, tables[:, nz + b].contiguous(), K, NS, p, B, H) for b in range(nz)] if spade else []
             lz_b = [P[f"lin_z.{b}.bias"].detach().to(F32) for b in range(nz)]
@@ -167,7 +140,7 @@ class _FieldTrainLayers(torch.autograd.Function):
                                   operand_max=amax[2 * b + 1:], blob=blob, layer=3 + 2 * b, bias=b1[b], add1=x,
                                   out=Xpre[b + 1], partial=part, **lin_z(b + 1)), stream)
             # lin_out + sigmoid / relu in one pass (max relu(x) for its weight gradient; relu(x) not stored)
-            out, a_max = lin_out_rows(Xpre[nb], P["lin_out.weight"].detach(), P["lin_out.bias"].detach())
+            out, a_max = ops.lin_out_rows(Xpre[nb], P["lin_out.weight"].detach(), P["lin_out.bias"].detach())
             out = out.reshape(SB, B, 4)
         ctx.fused, ctx.coarse, ctx.names, ctx.entry = fused, coarse, names, entry
         ctx.keep = (Xpre, Xin, N, S, amax, zfp, a_max, idt, p, cl)
@@ -177,9 +150,6 @@ class _FieldTrainLayers(torch.autograd.Function):
     @staticmethod
     def backward(ctx, grad_out):
         from .bn_train import _layer, _partial, _run
-        from .models import combine_interleaved
-        from .field import _feat_grad
-        from .ops import _max_bits, lin_out_rows_bwd, spade_bwd_rows, sum_of_products, weight_grads
         xyz, viewdirs, latent, out, *params = ctx.saved_tensors
         Xpre, Xin, N, S, amax, zfp, a_max, idt, p, cl = ctx.keep
         ctx.keep = None
@@ -187,7 +157,7 @@ class _FieldTrainLayers(torch.autograd.Function):
         net = fused.net
         mlp = fused._mlp(ctx.coarse)
         P = dict(zip(names, params))
-        dims = entry.dims
+        dims = entry.dims.with_precision(_lib.FIELD_X3)
         H, nb, nz = dims.d_hidden, dims.n_blocks, dims.n_lin_z
         spade = bool(dims.spade)
         NS = net.num_views_per_obj
@@ -202,8 +172,8 @@ class _FieldTrainLayers(torch.autograd.Function):
             bwd = fused.packed_bwd(ctx.coarse, entry)
             part = _partial(M1, H, dev)
             # the activations' backward (d4), lin_out^T and its relu's backward in one pass
-            d4, g, d4_max = lin_out_rows_bwd(grad_out.reshape(M2, 4), out.reshape(M2, 4),
-                                             P["lin_out.weight"].detach(), Xpre[nb])
+            d4, g, d4_max = ops.lin_out_rows_bwd(grad_out.reshape(M2, 4), out.reshape(M2, 4),
+                                                 P["lin_out.weight"].detach(), Xpre[nb])
             wl1, wl2 = [], []           # weight-gradient layers over M1 / M2 rows
             Gz, Gs, Gz_max, Gs_max = [None] * nz, [None] * nz, [None] * nz, [None] * nz
             blk = [None] * nb
@@ -245,31 +215,31 @@ class _FieldTrainLayers(torch.autograd.Function):
                     Gz_max[b] = fc0t_max[b:b + 1]
                     if spade:                                  # X' = S * X + T (models.py:585-587)
                         # dS = g * X (+ its max for scale_z's weight gradient), dX = S * g: one pass
-                        Gs[b], gin, Gs_max[b] = spade_bwd_rows(Gz[b], Xpre[b].contiguous(), S[b])
+                        Gs[b], gin, Gs_max[b] = ops.spade_bwd_rows(Gz[b], Xpre[b].contiguous(), S[b])
                 g = gin.contiguous()
             g_in0 = g                                          # d loss / d lin_in output
             for b in range(nb):
                 (wl1 if b < cl else wl2).extend(blk[b])
-            g_in0_max = fc0t_max[0:1] if in0_direct else _max_bits(g_in0)
+            g_in0_max = fc0t_max[0:1] if in0_direct else ops._max_bits(g_in0)
             lat_feat = None
             if nz > 0:
                 hwc = fused.latent_hwc_all(latent)
                 if hwc.shape[0] != K:    # one map shared by the scenes (or more maps than scenes)
                     hwc = hwc[torch.clamp(torch.arange(K, device=dev), max=hwc.shape[0] - 1)].contiguous()
-                lat_feat = _gather(fused, hwc, K, NS, p, B, net.d_latent)
+                lat_feat = _gather(fused, hwc, K, NS, p, B, net.d_latent)   # (lookup_features' batched launches)
                 lat_max = fused.latent_max_bits(latent)
                 for b in range(nz):
                     zmax = Gz_max[b]
                     wl1.append((Gz[b], lat_feat, zmax, lat_max, True))
                 for b in range(nz if spade else 0):
                     wl1.append((Gs[b], lat_feat, Gs_max[b], lat_max, True))
-            wl1.append((g_in0, zfp, g_in0_max, _max_bits(zfp), True))
+            wl1.append((g_in0, zfp, g_in0_max, ops._max_bits(zfp), True))
             wl2.append((d4, Xpre[nb], d4_max, a_max, True, relu_x))
             if M1 == M2:     # one source view: every layer over the same rows, one launch
-                r = weight_grads(wl1 + wl2, M1)
+                r = ops.weight_grads(wl1 + wl2, M1)
                 r1, r2 = r[:len(wl1)], r[len(wl1):]
             else:
-                r1, r2 = weight_grads(wl1, M1), weight_grads(wl2, M2)
+                r1, r2 = ops.weight_grads(wl1, M1), ops.weight_grads(wl2, M2)
             grads = {"lin_out.weight": r2[-1][0], "lin_out.bias": r2[-1][1]}
             i1, i2 = 0, 0
             for b in range(nb):
@@ -289,31 +259,18 @@ class _FieldTrainLayers(torch.autograd.Function):
                 i1 += 1
             w_in, c_in = r1[i1]
             grads["lin_in.weight"], grads["lin_in.bias"] = w_in[:, :net.d_in].contiguous(), c_in
-        d_latent = d_xyz = None
-        if want_latent or want_xyz:
-            with torch.enable_grad():
-                lat = latent.detach().requires_grad_(want_latent)
-                x = xyz.detach().requires_grad_(want_xyz)
-                feat, zft = net.mlp_inputs(x, viewdirs.detach(), latent=lat)
-                outs, grads_out = [], []
-                # with stop_encoder_grad the looked-up latent is detached (models.py:810-811): no gradient reaches
-                # the points through the lookup, z_feature's part alone (as avr.field._FieldTrain)
-                if nz > 0 and not net.stop_encoder_grad:
-                    outs.append(feat)
-                    if spade:
-                        pairs = [(Gz[b], P[f"lin_z.{b}.weight"].detach()) for b in range(nz)]
-                        pairs += [(Gs[b], P[f"scale_z.{b}.weight"].detach()) for b in range(nz)]
-                        grads_out.append(sum_of_products(pairs))
-                    else:   # the lin_z^T layers on the x3 layer GEMM where they apply (avr.field._feat_grad)
-                        grads_out.append(_feat_grad(fused, entry, bwd, Gz, P, M1))
-                if want_xyz:
-                    outs.append(zft)
-                    grads_out.append(g_in0 @ P["lin_in.weight"].detach())
-                wrt = ([lat] if want_latent else []) + ([x] if want_xyz else [])
-                res_in = torch.autograd.grad(outs, wrt, grads_out, allow_unused=True)
-            if want_latent:
-                d_latent = res_in[0] if res_in[0] is not None else torch.zeros_like(latent)
-            if want_xyz:
-                d_xyz = res_in[-1] if res_in[-1] is not None else torch.zeros_like(xyz)
+        g_feat = g_zf = None
+        # with stop_encoder_grad the looked-up latent is detached (models.py:810-811): no gradient reaches the
+        # points through the lookup, z_feature's part alone (as avr.field._FieldTrain)
+        if (want_latent or want_xyz) and nz > 0 and not net.stop_encoder_grad:
+            if spade:
+                pairs = [(Gz[b], P[f"lin_z.{b}.weight"].detach()) for b in range(nz)]
+                pairs += [(Gs[b], P[f"scale_z.{b}.weight"].detach()) for b in range(nz)]
+                g_feat = ops.sum_of_products(pairs)
+            else:   # the lin_z^T layers on the x3 layer GEMM where they apply (avr.field._feat_grad)
+                g_feat = _feat_grad(fused, entry, bwd, Gz, P, M1)
+        if want_xyz:
+            g_zf = g_in0 @ P["lin_in.weight"].detach()
+        d_latent, d_xyz = input_grads_via_autograd(net, xyz, viewdirs, latent, want_latent, want_xyz, g_feat, g_zf)
         return (None, None, None, d_xyz, None, d_latent) + tuple(
             grads[n] if ctx.needs_input_grad[6 + i] else None for i, n in enumerate(names))

@@ -53,7 +53,7 @@ def _capture_forward(layer_train, store):
     """Wrap _FieldTrainLayers.forward so each call appends what the HIP forward decided: its stored fp32 rows
     (Xpre[b]: block b's residual stream before lin_z / spade / combine, Xin[b]: block b's input, N[b]: fc_0's
     output) and its output. The relu masks and the max-combine's winning views of the HIP run are read from these
-    exactly as its backward reads them (layer_train.py:205-242). Returns the original forward."""
+    exactly as its backward reads them (layer_train.py:175-212). Returns the original forward."""
     orig = layer_train._FieldTrainLayers.forward
 
     def forward(ctx, fused, coarse, *rest):
@@ -68,8 +68,8 @@ def _capture_forward(layer_train, store):
 
 def _hip_masks(cap, mlp, SB, NS, B):
     """The branch of the piecewise-linear MLP the HIP forward took: relu masks [rows > 0] of every fc_0 / fc_1 /
-    lin_out operand and of sigma (the backward's masks, layer_train.py:205-233), and with the max combine the view
-    torch.max(dim) picks on the HIP rows (the one its adjoint, layer_train.py:238-242, sends the gradient to)."""
+    lin_out operand and of sigma (the backward's masks, layer_train.py:175-203), and with the max combine the view
+    torch.max(dim) picks on the HIP rows (the one its adjoint, layer_train.py:208-212, sends the gradient to)."""
     Xpre, Xin, N, out = cap
     nb = mlp.n_blocks
     m = {"x": [x > 0 for x in Xin], "n": [n > 0 for n in N], "out": Xpre[nb] > 0,
