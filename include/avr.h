@@ -532,7 +532,18 @@ int avr_raymarch(const avr_view_desc* view, const float* gate_table, const float
  * ABI 15: bit-deterministic by construction, no floating-point atomics -- the table gradient summed as int64
  * fixed-point values under one power-of-two scale per call (chosen from max |dg| so no sum can overflow; integer
  * sums do not depend on the order), then rounded once to fp32 (an entry a NaN / inf gate gradient reached is
- * NaN); the parameter gradients summed in a fixed order. `scratch` holds avr_raymarch_bwd_scratch_bytes(n, steps,
+ * NaN); the parameter gradients summed in a fixed order.
+ * Accuracy of d_tables: absolute, relative to the largest gate gradient of the call. With e the frexp exponent of
+ * max |dg| over the call's finite gate gradients and cbits = ceil(log2(4 * steps * n)), every contribution
+ * w_corner * dg (the exact product of the two fp32 values) is rounded once onto a grid of 2^(cbits + e - 62), so an
+ * entry that n_i lookups reach differs from the exact sum of its contributions by at most n_i * 2^(cbits + e - 63)
+ * <= n_i * 2^(cbits - 62) * max |dg|, plus the one rounding of the sum to fp32 (tests/test_gpu_march_kernels.py,
+ * test_fixed_point_*). For callers: entries below about 2^-22 of the call's largest are not accurate to fp32
+ * relative precision (a contribution below 2^(cbits - 62) of max |dg| is lost altogether); the table gradient is
+ * meant to be consumed at the scale of its largest entries, as W_ih's and the latent's gradients do. A ray whose
+ * gate gradients are NaN / inf (a NaN in its grad_world, say) makes the entries its lookups touch NaN and the
+ * parameter gradients non-finite, and changes no other table entry; steps = 0 (or n_per_scene = 0) writes d_tables and d_grads as exact zeros.
+ * `scratch` holds avr_raymarch_bwd_scratch_bytes(n, steps,
  * n_scenes * H*W * 64) bytes (n = n_scenes * n_per_scene; the accumulators, the stored gate gradients and
  * lookups, the workgroups' partials), scratch_bytes its size; lookup_grad 1 =
  * the lookup's position gradient flows into the points (models.py:753-823 with stop_encoder_grad False), 0 = it
