@@ -15,7 +15,9 @@ LIB_PATH = os.environ.get("AVR_LIB_PATH") or os.path.join(_HERE, "libavr_hip.so"
 AVR_MAX_BLOCKS = 8
 AVR_MAX_SCENES = 16
 AVR_LOOKUP_GRAD_TERMS = 8
-ABI_VERSION = 17
+ABI_VERSION = 18
+ADAM_CHUNK = 4096          # avr.h AVR_ADAM_CHUNK: elements per work chunk of avr_adam_step
+ADAM_MAX_TENSORS = 88      # avr.h AVR_ADAM_MAX_TENSORS: tensors per avr_adam_step launch
 
 
 def scene_groups(n):
@@ -93,6 +95,13 @@ class BnLayer(ctypes.Structure):
                 ("partial", c_void_p),
                 ("lin_z_table", c_void_p), ("lin_z_scene_stride", i64), ("xyz", c_void_p), ("views", c_void_p),
                 ("n_views", c_int), ("rows_per_scene", i64), ("out_max", c_void_p)]
+
+
+class AdamTensor(ctypes.Structure):
+    """avr_adam_tensor (ABI 18): five 8-byte fields, so a host array of them is also a flat int64 array
+    (ops.adam_step fills one without a ctypes object per field)."""
+    _fields_ = [("param", c_void_p), ("grad", c_void_p), ("exp_avg", c_void_p), ("exp_avg_sq", c_void_p),
+                ("numel", i64)]
 
 
 # name -> argtypes (all return int status)
@@ -181,6 +190,9 @@ _SIGS = {
                      c_void_p, c_void_p, c_void_p, c_void_p],
     "avr_image_metrics_workspace_bytes": [i64, c_int, c_int, ctypes.POINTER(i64)],
     "avr_image_metrics": [c_void_p, c_void_p, i64, c_int, c_int, c_void_p, i64, c_void_p, c_void_p, c_void_p],
+    # tensors: an AdamTensor array, or the address of one (c_void_p takes both)
+    "avr_adam_step": [c_void_p, i64, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double,
+                      ctypes.c_double, c_void_p, c_void_p],
     "avr_stream_copy": [c_void_p, c_void_p, i64, c_void_p],
     "avr_stream_fill": [c_void_p, i64, c_uint32, c_void_p],
 }

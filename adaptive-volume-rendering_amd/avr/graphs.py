@@ -130,7 +130,8 @@ class GraphedTrainStep:
     and returns what the caller reads after the step (e.g. the loss; avr.losses.loss_fn is train.py's loss without
     the reference's host-side isnan test, which a capture refuses); it may call optimizer.zero_grad() (the
     default set_to_none: a host-only no-op once captured: the captured backward writes the gradients). The
-    optimizer must be capturable: torch.optim.Adam(..., capturable=True, fused=True) (the fused form is one
+    optimizer must be capturable: avr.optim.Adam(...) needs no flags (one HIP launch per 88 parameters, the step
+    count kept on the device); torch.optim.Adam needs capturable=True, fused=True (the fused form is one
     multi-tensor kernel; the capturable foreach form adds many small launches).
 
     Calls 1 .. warmup run step_fn eagerly (real steps, on a side stream, so the graph's memory pool starts clean);

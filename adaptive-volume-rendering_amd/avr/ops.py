@@ -3,6 +3,7 @@
 All tensors are device tensors owned by PyTorch; every launch is enqueued on
 torch's current HIP stream. No function here has a host/CPU implementation.
 """
+import array
 import ctypes
 import functools
 
@@ -550,6 +551,22 @@ def latent_features(view, latent_chw, xyz, out=None, hwc=None):
     require_device(lat, xyz, out)
     call("avr_latent_features", ctypes.byref(view), ptr(lat), C, ptr(xyz), n, ptr(out), stream_of(xyz))
     return out
+
+
+def adam_step(tensors, lr, beta1, beta2, eps, weight_decay, step):
+    """One Adam step (train.py:112-114, :299) of `tensors`, a list of (param, grad, exp_avg, exp_avg_sq) fp32
+    device tensors whose four members share one dense element order, in place; `step` is the 0-dim fp32 device
+    counter the kernel reads and advances (avr_adam_step: one launch per _lib.ADAM_MAX_TENSORS tensors and one for
+    the counter, no host read, capturable). The caller answers for dtype, device and layout (avr.optim.Adam
+    checks them per parameter)."""
+    if not tensors:
+        return
+    require_device(step)
+    flat = array.array("q")
+    for p, g, m, v in tensors:
+        flat.extend((p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel()))
+    call("avr_adam_step", flat.buffer_info()[0], len(tensors), lr, beta1, beta2, eps, weight_decay, ptr(step),
+         stream_of(step))
 
 
 def stream_copy(src, dst):

@@ -24,10 +24,12 @@
 extern "C" {
 #endif
 
-#define AVR_ABI_VERSION 17
+#define AVR_ABI_VERSION 18
 #define AVR_MAX_BLOCKS 8
 #define AVR_LOOKUP_GRAD_TERMS 8   /* tables per avr_latent_tables_grad_points call */
 #define AVR_MAX_SCENES 16   /* scenes per training-forward launch */
+#define AVR_ADAM_CHUNK 4096        /* elements per work chunk of avr_adam_step; exported so tests can place sizes around it */
+#define AVR_ADAM_MAX_TENSORS 88    /* tensors per avr_adam_step launch (what the 4 KB kernel-argument block holds) */
 
 enum {
   AVR_OK = 0,
@@ -599,6 +601,38 @@ int avr_loss_bwd(int64_t n_rays, int terms, const float* rgb_c, const float* rgb
 int avr_image_metrics_workspace_bytes(int64_t n_frames, int height, int width, int64_t* n_bytes);
 int avr_image_metrics(const float* img, const float* gt, int64_t n_frames, int height, int width, void* workspace,
                       int64_t workspace_bytes, float* psnr, float* ssim, void* stream);
+
+/* ---------------------------------------------------------------- optimizer
+ * ABI 18: optimizer.step() of train.py:112-114 with the torch.optim.Adam of train.py:299, for a list of fp32
+ * tensors. Per element, in the order of torch's _single_tensor_adam, every operation rounded once to fp32:
+ *   g = grad (+ weight_decay * p   if weight_decay != 0)
+ *   m = m + (g - m) * (1 - beta1)
+ *   v = v * beta2 + ((1 - beta2) * g) * g
+ *   t = step + 1
+ *   p = p + -(lr / (1 - beta1^t)) * (m / (sqrt(v) / sqrt(1 - beta2^t) + eps))
+ * `tensors` is a HOST array of n_tensors entries; param, grad, exp_avg, exp_avg_sq are device pointers to numel
+ * contiguous floats each (the same element order in all four). The list is copied into the kernel arguments
+ * (AVR_ADAM_MAX_TENSORS entries per launch; a longer list takes several launches), so the array may be freed on
+ * return and a captured launch reads no host memory. A tensor whose four pointers are all 16-B aligned is
+ * read and written 16 B per lane; any other, and a tail of fewer than 4 elements, 4 B per lane. `step` is the
+ * step counter, one float in DEVICE memory that the host never reads: the update launches read it and compute the
+ * two bias-correction factors from it in fp64 (beta^t by squaring), rounded once to fp32; a trailing one-wave
+ * launch then advances it by 1, once per call, so no launch reads the counter while another workgroup writes it.
+ * ceil(non-empty tensors / AVR_ADAM_MAX_TENSORS) + 1 launches per call; nothing is allocated, nothing
+ * synchronises: the call can be recorded in a HIP-graph capture, which bakes in the hyper-parameters.
+ * NaN and inf in a gradient propagate as the formula does (no guard, no skipped step).
+ * Checked before any HIP call: n_tensors == 0 is a no-op that leaves `step` untouched; n_tensors < 0, a null
+ * `tensors` or `step`, numel < 0, a null pointer in an entry with numel > 0, lr < 0, a beta outside [0, 1),
+ * eps < 0 and weight_decay < 0 return AVR_E_INVALID. An entry with numel == 0 is skipped.                       */
+typedef struct {
+  float* param;
+  const float* grad;
+  float* exp_avg;
+  float* exp_avg_sq;
+  int64_t numel;
+} avr_adam_tensor;
+int avr_adam_step(const avr_adam_tensor* tensors, int64_t n_tensors, double lr, double beta1, double beta2, double eps,
+                  double weight_decay, float* step, void* stream);
 
 /* ------------------------------------------------------------ measurement
  * Streaming device copy dst[0, n_bytes) = src[0, n_bytes) (16-B aligned,
