@@ -38,6 +38,24 @@ int check_launch(const char* what);
 
 inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
 
+// Launch kernel K with `shm` bytes of dynamic LDS on a (blocks, gy, gz) grid. K is a template argument, so each
+// kernel instantiation has its own once-flag: its first launch raises the kernel's dynamic-LDS limit to shm_max,
+// the most K is ever launched with. `too_many`: the error text for a grid x past 2^31 - 1.
+template <auto K, typename... Args>
+int launch_lds(const char* name, const char* too_many, int64_t blocks, unsigned gy, unsigned gz, int threads,
+               size_t shm, size_t shm_max, hipStream_t s, const Args&... args) {
+  static bool attr = false;
+  if (!attr) {
+    if (hipFuncSetAttribute(reinterpret_cast<const void*>(K), hipFuncAttributeMaxDynamicSharedMemorySize,
+                            (int)shm_max) != hipSuccess)
+      return fail(AVR_E_HIP, "%s: cannot set dynamic LDS to %zu", name, shm_max);
+    attr = true;
+  }
+  AVR_REQUIRE(blocks < (1ll << 31), "%s", too_many);
+  K<<<dim3((unsigned)blocks, gy, gz), threads, shm, s>>>(args...);
+  return check_launch(name);
+}
+
 constexpr int kWave = 64;
 
 // ------------------------------------------------------------------ fp32 ops

@@ -77,15 +77,6 @@ __device__ __forceinline__ void pair_to_lines(floatx4 x0, floatx4 x1, bool lo, f
   B = lo ? r : x1;
 }
 
-template <int FT, int NW, bool TWO>
-__device__ __forceinline__ void bn_gemm(floatx4 (&acc)[FT][4], FragX3 (&A0)[FT], const uint4* __restrict__ W, int KC,
-                                        int cstride, const uint4* X16, int lane) {
-  if constexpr (TWO)
-    gemm_x3_sg<FT, true, FT>(acc, A0, W, KC, cstride, X16, lane);
-  else
-    gemm_x3<FT, true, false>(acc, A0, W, KC, cstride, X16, lane);
-}
-
 // MODE 0 forward, 1 backward; KK = K (64: lin_in, or d_hidden). Workgroup = 64 rows, NW waves, no fp32 stage and
 // no epilogue barrier:
 // * operand: the K columns are 4 KK / 32 items (32-column chunk c, sample group sg of 16 rows); wave w takes IPW
@@ -260,7 +251,7 @@ __global__ void __launch_bounds__(64 * NW, NW > 4 ? 1 : 2) bn_layer_kernel(BnArg
 
   // ---------------------------------------------------------------- GEMM
   floatx4 acc[FT][4];
-  bn_gemm<FT, NW, TWO>(acc, A0, W, KK / 32, 64 * FT * NW, X16, lane);
+  gemm<FT, true, TWO>(acc, A0, W, KK / 32, 64 * FT * NW, X16, lane);
   const float inv = 1.0f / (pow2_scale_for(__uint_as_float(a.hdr[a.hdr_idx])) * s_x);
 
   // ---------------------------------------------------------------- epilogue
@@ -475,17 +466,8 @@ __global__ void __launch_bounds__(64 * NW, NW > 4 ? 1 : 2) bn_layer_kernel(BnArg
 template <int FT, int NW, int MODE, int KK>
 static int launch_bn_layer(const BnArgs& a, hipStream_t s) {
   const size_t shm = (size_t)64 * KK * 4 + 64;   // X (64 samples x KK x hi + lo fp16) + the wave maxima
-  static bool attr = false;
-  if (!attr) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&bn_layer_kernel<FT, NW, MODE, KK>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm) != hipSuccess)
-      return fail(AVR_E_HIP, "bn_layer_kernel: cannot set dynamic LDS");
-    attr = true;
-  }
-  const int64_t blocks = (a.M + kX3Samples - 1) / kX3Samples;
-  AVR_REQUIRE(blocks < (1ll << 31), "avr_bn_layer_run: too many rows");
-  bn_layer_kernel<FT, NW, MODE, KK><<<(unsigned)blocks, 64 * NW, shm, s>>>(a);
-  return check_launch("bn_layer_kernel");
+  return launch_lds<bn_layer_kernel<FT, NW, MODE, KK>>("bn_layer_kernel", "avr_bn_layer_run: too many rows",
+                                                      (a.M + kX3Samples - 1) / kX3Samples, 1, 1, 64 * NW, shm, shm, s, a);
 }
 
 // K is lin_in's 64 (forward) or d_hidden
@@ -501,13 +483,9 @@ static int launch_bn_layer_k(const BnArgs& a, hipStream_t s) {
 
 template <int MODE>
 static int dispatch_bn_layer(int H, const BnArgs& a, hipStream_t s) {
-  switch (H) {
-    case 64: return launch_bn_layer_k<1, 4, MODE>(a, s);
-    case 128: return launch_bn_layer_k<2, 4, MODE>(a, s);
-    case 256: return launch_bn_layer_k<4, 4, MODE>(a, s);
-    case 512: return launch_bn_layer_k<4, 8, MODE>(a, s);
-  }
-  return fail(AVR_E_UNSUPPORTED, "avr_bn_layer_run: d_hidden %d", H);
+  return x3_width<8>(H, true, "avr_bn_layer_run", [&](auto ft, auto nw) {
+    return launch_bn_layer_k<decltype(ft)::value, decltype(nw)::value, MODE>(a, s);
+  });
 }
 
 // ------------------------------------------------------------------ finalize

@@ -6,7 +6,7 @@
 // 16x16 accumulator tile (lane l: sample l&15, features 4(l>>4)+0..3) is
 // already in the lane order the next layer's B operand wants:
 //   k-step (t, r) uses feature 16t + 4g + r from lane group g = l>>4.
-// Weights are repacked once (avr_field_pack) into that fragment order,
+// Weights are repacked once (avr_field_pack, field_pack.hip) into that fragment order,
 // [t][ot][lane] float4 = W[16ot + (l&15)][16t + 4(l>>4) + 0..3], so each lane
 // streams 16 B per 4 MFMAs with fully coalesced 1 KiB wave loads.
 //
@@ -19,210 +19,13 @@
 // lin_z is applied to the latent map per texel (avr_field_latent_table) and
 // bilinearly interpolated per sample; every bias (b_in + bz0, b1 + bz_{b+1},
 // ...) is pre-summed at pack time.
-#include <mutex>
-
+//
+// This file: the fp32 MFMA field kernel, the per-texel latent tables, and the C entry points of the field's
+// forward and backward passes in both precisions (the x3 kernels are in field_x3.hip / field_bwd.hip, the
+// blob layouts and the pack in field_pack.hip).
 #include "field_common.h"
 
 namespace avr {
-
-// ----------------------------------------------------------------- layout
-static int make_layout(const avr_field_dims* d, Layout* L) {
-  AVR_REQUIRE(d, "field: null dims");
-  AVR_REQUIRE(d->d_hidden == 64 || d->d_hidden == 128 || d->d_hidden == 256 || d->d_hidden == 512,
-              "field: d_hidden must be 64/128/256/512 (got %d)", d->d_hidden);
-  AVR_REQUIRE(d->d_latent > 0 && d->d_latent % 16 == 0 && d->d_latent <= 1024,
-              "field: d_latent must be a positive multiple of 16 <= 1024 (got %d)", d->d_latent);
-  AVR_REQUIRE(d->n_blocks >= 1 && d->n_blocks <= AVR_MAX_BLOCKS, "field: n_blocks must be in [1, %d]",
-              AVR_MAX_BLOCKS);
-  AVR_REQUIRE(d->n_lin_z >= 0 && d->n_lin_z <= d->n_blocks, "field: n_lin_z must be in [0, n_blocks]");
-  AVR_REQUIRE(d->num_freqs >= 0 && 3 + 6 * d->num_freqs + 3 == d->d_in && d->d_in <= 16 * kInTiles,
-              "field: d_in %d != 6*num_freqs+6 or > 48 (fused path supports PE(xyz)+raw viewdirs)", d->d_in);
-  const int NT = d->d_hidden / 16, KC = d->d_hidden / 32;
-  L->NT = NT;
-  L->KTl = d->d_latent / 16;
-  const int64_t tile = 64 * 4;  // floats per (t, ot) fp32 fragment block
-  const int64_t tile16 = 64 * 8;  // floats per (c, ft) fp16 hi/lo fragment block (64 lanes x 32 B)
-  int64_t o = 0;
-  L->w_in = o; o += (int64_t)kInTiles * NT * tile;
-  for (int b = 0; b < d->n_blocks; ++b) {
-    L->fc0[b] = o; o += (int64_t)NT * NT * tile;
-    L->fc1[b] = o; o += (int64_t)NT * NT * tile;
-  }
-  L->w_out = o; o += (int64_t)NT * tile;
-  for (int b = 0; b < d->n_lin_z; ++b) { L->lin_z[b] = o; o += (int64_t)L->KTl * NT * tile; }
-  L->b_in = o; o += d->d_hidden;
-  for (int b = 0; b < d->n_blocks; ++b) {
-    L->b_fc0[b] = o; o += d->d_hidden;
-    L->b_fc1[b] = o; o += d->d_hidden;
-  }
-  L->b_out = o; o += 16;
-  o = (o + 63) & ~(int64_t)63;
-  L->x3_hdr = o; o += 64;
-  L->x3_in = o; o += (int64_t)kX3InChunks * NT * tile16;
-  for (int b = 0; b < d->n_blocks; ++b) {
-    L->x3_fc0[b] = o; o += (int64_t)KC * NT * tile16;
-    L->x3_fc1[b] = o; o += (int64_t)KC * NT * tile16;
-  }
-  L->x3_out = o; o += (int64_t)KC * tile16;
-  AVR_REQUIRE(d->bn == 0 || d->bn == 1, "field: bn must be 0 or 1");
-  L->bn = d->bn;
-  for (int b = 0; b < d->n_blocks; ++b) {
-    L->bn_a[b] = L->bn_c[b] = 0;
-    if (d->bn) { L->bn_a[b] = o; o += d->d_hidden; L->bn_c[b] = o; o += d->d_hidden; }
-  }
-  AVR_REQUIRE(d->spade == 0 || d->spade == 1, "field: spade must be 0 or 1");
-  AVR_REQUIRE(d->beta >= 0.f && d->beta < 1e30f, "field: beta must be >= 0 (0: ReLU)");
-  AVR_REQUIRE(!(d->beta > 0.f && d->bn), "field: Softplus with BatchNorm runs on the module path");
-  AVR_REQUIRE(!(d->spade && d->bn), "field: use_spade with BatchNorm runs on the module path");
-  L->spade = d->spade;
-  L->n_lin_z = d->n_lin_z;
-  L->n_tables = d->n_lin_z * (d->spade ? 2 : 1);
-  for (int b = 0; b < AVR_MAX_BLOCKS; ++b) L->scale_z[b] = 0;
-  for (int t = 0; t < 2 * AVR_MAX_BLOCKS; ++t) L->b_tab[t] = 0;
-  if (d->spade) {
-    for (int b = 0; b < d->n_lin_z; ++b) { L->scale_z[b] = o; o += (int64_t)L->KTl * NT * tile; }
-    for (int t = 0; t < L->n_tables; ++t) { L->b_tab[t] = o; o += d->d_hidden; }
-  }
-  L->x3_tables = d->d_latent % 64 == 0 && d->d_latent <= 512;
-  for (int t = 0; t < 2 * AVR_MAX_BLOCKS; ++t) L->x3_tab[t] = 0;
-  for (int t = 0; L->x3_tables && t < L->n_tables; ++t) {
-    L->x3_tab[t] = o;
-    o += (int64_t)(d->d_latent / 32) * NT * tile16;
-  }
-  L->total = o;
-  return AVR_OK;
-}
-
-static int make_bwd_layout(const avr_field_dims* d, BwdLayout* LB) {
-  const int64_t S = (int64_t)(d->d_hidden / 32) * (d->d_hidden / 16) * 64 * 8;   // floats per x3 hidden layer
-  int64_t o = 64;
-  for (int b = 0; b < d->n_blocks; ++b) {
-    LB->fc0t[b] = o; o += S;
-    LB->fc1t[b] = o; o += S;
-  }
-  // lin_z[b]^T (d_latent x d_hidden after the transpose: a hidden layer's shape when d_latent == d_hidden) for
-  // avr_bn_layer_run's transposed products (the point gradient's sum_b Gz[b] . W_z[b])
-  for (int b = 0; b < AVR_MAX_BLOCKS; ++b) {
-    LB->lzt[b] = -1;
-    if (b < d->n_lin_z && d->d_latent == d->d_hidden && !d->spade) { LB->lzt[b] = o; o += S; }
-  }
-  LB->total = o;
-  return AVR_OK;
-}
-
-int field_layout(const avr_field_dims* d, Layout* L) { return make_layout(d, L); }
-int field_bwd_layout(const avr_field_dims* d, BwdLayout* LB) {
-  Layout L;
-  const int rc = make_layout(d, &L);
-  return rc ? rc : make_bwd_layout(d, LB);
-}
-
-// ----------------------------------------------------------------- packing
-// fp32 fragments: dst[(t*NTo + ot)*64 + l][r] = W[16ot + (l&15)][16t + 4(l>>4) + r] (zero padded);
-// bias vectors: dst[i] = a[i] + b[i] (b may be null), zero beyond n.
-// The fp32 fragments and bias vectors of a pack in two launches (blockIdx.y = job), not one launch each:
-// the pack runs in every training step (the weights change).
-struct LinJob {
-  const float* W;
-  float* dst;
-  int out_dim, in_dim, NTo, KTi;
-};
-struct LinBatch {
-  LinJob j[2 + 4 * AVR_MAX_BLOCKS];
-  int count;
-};
-struct BiasJob {
-  const float* a;
-  const float* b;
-  float* dst;
-  int n, n_pad;
-};
-struct BiasBatch {
-  BiasJob j[2 + 8 * AVR_MAX_BLOCKS];
-  int count;
-};
-
-__global__ void pack_linear_batch_kernel(LinBatch bt) {
-  const LinJob& J = bt.j[blockIdx.y];
-  const int64_t n = (int64_t)J.KTi * J.NTo * 256;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-    const int r = (int)(i & 3);
-    const int l = (int)((i >> 2) & 63);
-    const int64_t blk = i >> 8;
-    const int ot = (int)(blk % J.NTo), t = (int)(blk / J.NTo);
-    const int row = 16 * ot + (l & 15), col = 16 * t + 4 * (l >> 4) + r;
-    J.dst[i] = (row < J.out_dim && col < J.in_dim) ? J.W[(int64_t)row * J.in_dim + col] : 0.f;
-  }
-}
-
-__global__ void pack_bias_batch_kernel(BiasBatch bt) {
-  const BiasJob& J = bt.j[blockIdx.y];
-  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < J.n_pad; i += gridDim.x * blockDim.x)
-    J.dst[i] = (i < J.n) ? (J.b ? fadd(J.a[i], J.b[i]) : J.a[i]) : 0.f;
-}
-
-
-// x3 fragments: dst[((c*FTt + ft)*2 + {0, 1})*512 + 8l + e] = (hi, lo) of
-// (a tile's 64 hi lanes, then its 64 lo lanes: each 16-B-per-lane load of one
-// half reads 1 KiB contiguous, whole 128-B lines)
-// W[16ft + (l&15)][32c + (e<4 ? 4g+e : 16+4g+e-4)] * s_w, g = l>>4, with
-// s_w = 2^(14 - ceil-exponent of max|W|) from the layer's header word.
-// (rs, cs) = element strides of W's rows / columns: (in_dim, 1) for W, (1, ld) for W^T.
-__device__ __forceinline__ void pack_x3_elem(const float* __restrict__ W, int out_dim, int in_dim, int64_t rs,
-                                             int64_t cs, int FTt, const unsigned* __restrict__ maxbits,
-                                             _Float16* __restrict__ dst, int64_t i) {
-  const int e = (int)(i & 7);
-  const int l = (int)((i >> 3) & 63);
-  const int64_t blk = i >> 9;
-  const int ft = (int)(blk % FTt), c = (int)(blk / FTt);
-  const int g = l >> 4;
-  const int row = 16 * ft + (l & 15);
-  const int col = 32 * c + (e < 4 ? 4 * g + e : 16 + 4 * g + (e - 4));
-  const float sw = pow2_scale_for(__uint_as_float(*maxbits));
-  const float v = (row < out_dim && col < in_dim) ? W[(int64_t)row * rs + (int64_t)col * cs] * sw : 0.f;
-  const _Float16 hi = (_Float16)v;
-  const _Float16 lo = (_Float16)(v - (float)hi);
-  const int64_t base = ((int64_t)c * FTt + ft) * 2 * 64 * 8 + l * 8;
-  dst[base + e] = hi;
-  dst[base + 64 * 8 + e] = lo;
-}
-
-// Every layer of a pack in two launches (max |W| of each layer, then its
-// fragments; blockIdx.y = layer) instead of two per layer: the weight pack
-// runs in every training step.
-struct X3PackJob {
-  const float* W;
-  unsigned* maxbits;
-  _Float16* dst;
-  int64_t rs, cs, nw, n;
-  int out_dim, in_dim, FTt;
-};
-struct X3PackBatch {
-  X3PackJob j[kX3PackJobs];
-  int count;
-};
-
-// max|W| of each layer as float bits (atomicMax on non-negative floats = on their bits)
-// (one atomic per workgroup: a few dozen per layer, not one per wave)
-__global__ void absmax_batch_kernel(X3PackBatch b) {
-  __shared__ float wm[4];
-  const X3PackJob& J = b.j[blockIdx.y];
-  float m = 0.f;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < J.nw; i += (int64_t)gridDim.x * blockDim.x)
-    m = fmaxf(m, fabsf(J.W[i]));
-#pragma unroll
-  for (int d = 32; d > 0; d >>= 1) m = fmaxf(m, __shfl_xor(m, d, 64));
-  if ((threadIdx.x & 63) == 0) wm[threadIdx.x >> 6] = m;
-  __syncthreads();
-  if (threadIdx.x == 0)
-    atomicMax(J.maxbits, __float_as_uint(fmaxf(fmaxf(wm[0], wm[1]), fmaxf(wm[2], wm[3]))));
-}
-
-__global__ void pack_x3_batch_kernel(X3PackBatch b) {
-  const X3PackJob& J = b.j[blockIdx.y];
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < J.n; i += (int64_t)gridDim.x * blockDim.x)
-    pack_x3_elem(J.W, J.out_dim, J.in_dim, J.rs, J.cs, J.FTt, J.maxbits, J.dst, i);
-}
 
 // ----------------------------------------------------------------- fp32 MFMA tiles
 // acc[ot] += sum_t sum_r A(ot,t,r) B(t,r); A from packed global [t][ot][lane]
@@ -442,92 +245,28 @@ __global__ void __launch_bounds__(256) latent_table_split_kernel(const float* __
 }
 
 // ----------------------------------------------------------------- host side
-static int pack_linear(const float* W, int out_dim, int in_dim, int NTo, int KTi, float* dst, LinBatch& bt) {
-  AVR_REQUIRE(W, "avr_field_pack: null weight tensor");
-  AVR_REQUIRE(bt.count < (int)(sizeof(bt.j) / sizeof(bt.j[0])), "avr_field_pack: too many layers");
-  bt.j[bt.count++] = LinJob{W, dst, out_dim, in_dim, NTo, KTi};
-  return AVR_OK;
-}
-
-// one layer into a batch (W is (out_dim, in_dim) row-major; transpose: (in_dim,
-// out_dim), and the fragments hold W^T)
-static int add_x3(X3PackBatch& bt, const float* W, int out_dim, int in_dim, int KC, int FTt, unsigned* maxbits,
-                  float* dst, bool transpose = false) {
-  AVR_REQUIRE(W, "avr_field_pack: null weight tensor");
-  AVR_REQUIRE(bt.count < kX3PackJobs, "avr_field_pack: too many layers");
-  X3PackJob& J = bt.j[bt.count++];
-  J.W = W;
-  J.maxbits = maxbits;
-  J.dst = reinterpret_cast<_Float16*>(dst);
-  J.rs = transpose ? 1 : in_dim;
-  J.cs = transpose ? out_dim : 1;
-  J.nw = (int64_t)out_dim * in_dim;
-  J.n = (int64_t)KC * FTt * 64 * 8;
-  J.out_dim = out_dim;
-  J.in_dim = in_dim;
-  J.FTt = FTt;
-  return AVR_OK;
-}
-
-static int run_x3(const X3PackBatch& bt, hipStream_t s) {
-  if (bt.count == 0) return AVR_OK;
-  int64_t nw = 0, n = 0;
-  for (int k = 0; k < bt.count; ++k) {
-    nw = bt.j[k].nw > nw ? bt.j[k].nw : nw;
-    n = bt.j[k].n > n ? bt.j[k].n : n;
+// d_hidden -> NT = d_hidden / 16 output tiles of the fp32 kernels: f(NT) is called with an integral constant
+template <typename F>
+static int fp32_width(int d_hidden, F f) {
+  using std::integral_constant;
+  switch (d_hidden) {
+    case 64: return f(integral_constant<int, 4>{});
+    case 128: return f(integral_constant<int, 8>{});
+    case 256: return f(integral_constant<int, 16>{});
+    case 512: return f(integral_constant<int, 32>{});
   }
-  const unsigned ga = (unsigned)((nw + 4095) / 4096 < 64 ? (nw + 4095) / 4096 : 64);   // >= 16 values per thread
-  absmax_batch_kernel<<<dim3(ga, bt.count), 256, 0, s>>>(bt);
-  int rc = check_launch("absmax_batch_kernel");
-  if (rc) return rc;
-  const unsigned gp = (unsigned)((n + 255) / 256 < 1024 ? (n + 255) / 256 : 1024);
-  pack_x3_batch_kernel<<<dim3(gp, bt.count), 256, 0, s>>>(bt);
-  return check_launch("pack_x3_batch_kernel");
-}
-
-static int pack_bias(const float* a, const float* b, int n, int n_pad, float* dst, BiasBatch& bt) {
-  AVR_REQUIRE(a, "avr_field_pack: null bias tensor");
-  AVR_REQUIRE(bt.count < (int)(sizeof(bt.j) / sizeof(bt.j[0])), "avr_field_pack: too many vectors");
-  bt.j[bt.count++] = BiasJob{a, b, dst, n, n_pad};
-  return AVR_OK;
-}
-
-static int run_fp32_packs(const LinBatch& lb, const BiasBatch& bb, hipStream_t s) {
-  int64_t n = 0;
-  for (int k = 0; k < lb.count; ++k) {
-    const int64_t nk = (int64_t)lb.j[k].KTi * lb.j[k].NTo * 256;
-    n = nk > n ? nk : n;
-  }
-  if (lb.count) {
-    pack_linear_batch_kernel<<<dim3((unsigned)((n + 255) / 256 < 1024 ? (n + 255) / 256 : 1024), lb.count), 256, 0,
-                               s>>>(lb);
-    const int rc = check_launch("pack_linear_batch_kernel");
-    if (rc) return rc;
-  }
-  int nb = 0;
-  for (int k = 0; k < bb.count; ++k) nb = bb.j[k].n_pad > nb ? bb.j[k].n_pad : nb;
-  if (bb.count == 0) return AVR_OK;
-  pack_bias_batch_kernel<<<dim3((unsigned)((nb + 255) / 256), bb.count), 256, 0, s>>>(bb);
-  return check_launch("pack_bias_batch_kernel");
+  return fail(AVR_E_UNSUPPORTED, "field: d_hidden %d", d_hidden);
 }
 
 template <int NT>
 static int launch_field(const FieldArgs& a, hipStream_t s) {
   const size_t shm = (size_t)kFieldWaves * (NT > kInTiles ? NT : kInTiles) * 64 * sizeof(floatx4);
-  static bool attr = false;
-  if (!attr) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&field_fwd_kernel<NT>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm) != hipSuccess)
-      return fail(AVR_E_HIP, "field_fwd_kernel: cannot set dynamic LDS to %zu", shm);
-    attr = true;
-  }
   const int64_t per_block = kFieldWaves * kSPW;
-  const int64_t blocks = (a.M + per_block - 1) / per_block;
-  AVR_REQUIRE(blocks < (1ll << 31), "field: too many points");
-  field_fwd_kernel<NT><<<(unsigned)blocks, 64 * kFieldWaves, shm, s>>>(a);
-  return check_launch("field_fwd_kernel");
+  return launch_lds<field_fwd_kernel<NT>>("field_fwd_kernel", "field: too many points",
+                                          (a.M + per_block - 1) / per_block, 1, 1, 64 * kFieldWaves, shm, shm, s, a);
 }
 
+// (the dynamic-LDS limit is set per call on purpose: it depends on d_latent, which can grow between calls)
 template <int NT>
 static int launch_table(const float* packed, const Layout& L, const float* latent, int HW, int n_lin_z,
                         float* table, hipStream_t s) {
@@ -553,7 +292,7 @@ static int launch_table(const float* packed, const Layout& L, const float* laten
 static int field_common(const avr_field_dims* dims, const avr_view_desc* view, const float* packed,
                         const float* table, FieldArgs* a) {
   Layout L;
-  int rc = make_layout(dims, &L);
+  int rc = field_layout(dims, &L);
   if (rc) return rc;
   AVR_REQUIRE(view && packed, "field: null view/packed");
   AVR_REQUIRE(dims->n_lin_z == 0 || table, "field: null latent table");
@@ -575,38 +314,6 @@ static int field_common(const avr_field_dims* dims, const avr_view_desc* view, c
   return AVR_OK;
 }
 
-// The precision each blob was packed for (avr_field_pack): an AVR_FIELD_X3 blob holds no fp32 fragments of
-// lin_in / fc_0 / fc_1, so the fp32 kernel must not run on it. A small host-side table keyed by the blob's
-// address (the last kPackTags packs; the device header is not read back: that would synchronise the stream).
-namespace {
-constexpr int kPackTags = 128;
-struct PackTag {
-  const float* p;
-  int precision;
-};
-std::mutex g_pack_mu;
-PackTag g_pack_tags[kPackTags] = {};
-int g_pack_next = 0;
-
-void record_pack(const float* p, int precision) {
-  std::lock_guard<std::mutex> lock(g_pack_mu);
-  for (PackTag& t : g_pack_tags)
-    if (t.p == p) {
-      t.precision = precision;
-      return;
-    }
-  g_pack_tags[g_pack_next] = PackTag{p, precision};
-  g_pack_next = (g_pack_next + 1) % kPackTags;
-}
-
-int packed_precision(const float* p) {   // -1: not packed by this library instance (or evicted)
-  std::lock_guard<std::mutex> lock(g_pack_mu);
-  for (const PackTag& t : g_pack_tags)
-    if (t.p == p) return t.precision;
-  return -1;
-}
-}  // namespace
-
 static int dispatch_field(const avr_field_dims* dims, const FieldArgs& a, hipStream_t s) {
   const int d_hidden = dims->d_hidden;
   if (dims->precision == AVR_FIELD_X3) return dispatch_field_x3(d_hidden, a, s);
@@ -616,13 +323,7 @@ static int dispatch_field(const avr_field_dims* dims, const FieldArgs& a, hipStr
   AVR_REQUIRE(!dims->bn, "field: BatchNorm nets run on the x3 path only");
   AVR_REQUIRE(!dims->spade && !(dims->beta > 0.f), "field: use_spade / Softplus nets run on the x3 path only");
   AVR_REQUIRE(dims->precision == AVR_FIELD_FP32, "field: unknown precision %d", dims->precision);
-  switch (d_hidden) {
-    case 64: return launch_field<4>(a, s);
-    case 128: return launch_field<8>(a, s);
-    case 256: return launch_field<16>(a, s);
-    case 512: return launch_field<32>(a, s);
-  }
-  return fail(AVR_E_UNSUPPORTED, "field: d_hidden %d", d_hidden);
+  return fp32_width(d_hidden, [&](auto nt) { return launch_field<decltype(nt)::value>(a, s); });
 }
 
 }  // namespace avr
@@ -636,124 +337,24 @@ static int g_debug = 0;
 extern "C" void avr_debug_set_flags(int f) { g_debug = f; }
 #endif
 
-extern "C" int avr_field_packed_floats(const avr_field_dims* dims, int64_t* n_floats) {
-  Layout L;
-  const int rc = make_layout(dims, &L);
+// Several scenes in one launch (x3 path): scene s's samples are rows s * per_scene .. of the inputs, its lin_z
+// tables at tables + s * max(n_tables, 1) * H*W * d_hidden (FusedField.tables_batch), its view views[s].
+static int field_batch(const avr_field_dims* dims, const avr_view_desc* views, int n_scenes, const float* packed,
+                       const float* tables, FieldArgs* a, int64_t per_scene, const char* what) {
+  AVR_REQUIRE(views && n_scenes >= 1 && n_scenes <= AVR_MAX_SCENES, "%s: 1..%d scenes per call", what,
+              AVR_MAX_SCENES);
+  AVR_REQUIRE(dims && dims->precision == AVR_FIELD_X3, "%s: the multi-scene launch is x3 only", what);
+  int rc = field_common(dims, views, packed, tables, a);
   if (rc) return rc;
-  AVR_REQUIRE(n_floats, "avr_field_packed_floats: null output");
-  *n_floats = L.total;
-  return AVR_OK;
-}
-
-extern "C" int avr_field_pack(const avr_field_dims* dims, const avr_resnetfc_weights* w, float* packed,
-                              void* stream) {
-  Layout L;
-  int rc = make_layout(dims, &L);
-  if (rc) return rc;
-  AVR_REQUIRE(w && packed, "avr_field_pack: null pointer");
-  hipStream_t s = as_stream(stream);
-  const int H = dims->d_hidden, NT = L.NT;
-  // the fp32 fragments the x3 kernels never read (lin_in, fc_0, fc_1) are packed only for an fp32 blob; the
-  // lin_z / scale_z ones always (the exact-fp32 tables)
-  const bool fp32 = dims->precision != AVR_FIELD_X3, fp32_tab = true;
-  LinBatch lb{};
-  BiasBatch bb{};
-  if (fp32 && (rc = pack_linear(w->lin_in_w, H, dims->d_in, NT, kInTiles, packed + L.w_in, lb))) return rc;
-  if ((rc = pack_linear(w->lin_out_w, 4, H, 1, NT, packed + L.w_out, lb))) return rc;   // also the backward's
-  for (int b = 0; b < dims->n_blocks; ++b) {
-    if (fp32 && (rc = pack_linear(w->fc0_w[b], H, H, NT, NT, packed + L.fc0[b], lb))) return rc;
-    if (fp32 && (rc = pack_linear(w->fc1_w[b], H, H, NT, NT, packed + L.fc1[b], lb))) return rc;
-    if ((rc = pack_bias(w->fc0_b[b], nullptr, H, H, packed + L.b_fc0[b], bb))) return rc;
-    const float* bz = (b + 1 < dims->n_lin_z && !dims->spade) ? w->lin_z_b[b + 1] : nullptr;
-    if ((rc = pack_bias(w->fc1_b[b], bz, H, H, packed + L.b_fc1[b], bb))) return rc;
+  for (int s = 0; s < n_scenes; ++s) {
+    AVR_REQUIRE(views[s].latent_h == views[0].latent_h && views[s].latent_w == views[0].latent_w,
+                "%s: scenes need latent maps of one size", what);
+    view_from_desc(&views[s], &a->views[s]);
   }
-  for (int b = 0; fp32_tab && b < dims->n_lin_z; ++b)
-    if ((rc = pack_linear(w->lin_z_w[b], H, dims->d_latent, NT, L.KTl, packed + L.lin_z[b], lb))) return rc;
-  if ((rc = pack_bias(w->lin_in_b, dims->n_lin_z > 0 && !dims->spade ? w->lin_z_b[0] : nullptr, H, H,
-                      packed + L.b_in, bb)))
-    return rc;
-  for (int b = 0; dims->spade && b < dims->n_lin_z; ++b) {
-    AVR_REQUIRE(w->scale_z_w[b] && w->scale_z_b[b] && w->lin_z_b[b],
-                "avr_field_pack: use_spade needs scale_z weight / bias and lin_z bias of every lin_z block");
-    if (fp32_tab && (rc = pack_linear(w->scale_z_w[b], H, dims->d_latent, NT, L.KTl, packed + L.scale_z[b], lb)))
-      return rc;
-    if ((rc = pack_bias(w->lin_z_b[b], nullptr, H, H, packed + L.b_tab[b], bb))) return rc;
-    if ((rc = pack_bias(w->scale_z_b[b], nullptr, H, H, packed + L.b_tab[dims->n_lin_z + b], bb))) return rc;
-  }
-  if ((rc = pack_bias(w->lin_out_b, nullptr, 4, 16, packed + L.b_out, bb))) return rc;
-  for (int b = 0; dims->bn && b < dims->n_blocks; ++b) {
-    AVR_REQUIRE(w->bn_scale[b] && w->bn_shift[b], "avr_field_pack: bn needs bn_scale / bn_shift of every block");
-    if ((rc = pack_bias(w->bn_scale[b], nullptr, H, H, packed + L.bn_a[b], bb))) return rc;
-    if ((rc = pack_bias(w->bn_shift[b], nullptr, H, H, packed + L.bn_c[b], bb))) return rc;
-  }
-  if ((rc = run_fp32_packs(lb, bb, s))) return rc;
-  // split-fp16 fragments (header word per layer: 0 lin_in, 1 lin_out, 2+2b fc0[b], 3+2b fc1[b])
-  unsigned* hdr = reinterpret_cast<unsigned*>(packed + L.x3_hdr);
-  if (hipMemsetAsync(hdr, 0, 64 * sizeof(float), s) != hipSuccess) return fail(AVR_E_HIP, "avr_field_pack: memset");
-  const int KC = H / 32;
-  X3PackBatch bt{};
-  if ((rc = add_x3(bt, w->lin_in_w, H, dims->d_in, kX3InChunks, NT, hdr + 0, packed + L.x3_in))) return rc;
-  if ((rc = add_x3(bt, w->lin_out_w, 4, H, KC, 1, hdr + 1, packed + L.x3_out))) return rc;
-  for (int b = 0; b < dims->n_blocks; ++b) {
-    if ((rc = add_x3(bt, w->fc0_w[b], H, H, KC, NT, hdr + 2 + 2 * b, packed + L.x3_fc0[b]))) return rc;
-    if ((rc = add_x3(bt, w->fc1_w[b], H, H, KC, NT, hdr + 3 + 2 * b, packed + L.x3_fc1[b]))) return rc;
-  }
-  // the table weights for the x3 table kernel (lin_z[t], then scale_z with use_spade)
-  for (int t = 0; L.x3_tables && t < L.n_tables; ++t) {
-    const float* Wt = t < dims->n_lin_z ? w->lin_z_w[t] : w->scale_z_w[t - dims->n_lin_z];
-    if ((rc = add_x3(bt, Wt, H, dims->d_latent, dims->d_latent / 32, NT, hdr + kX3TabHdr + t, packed + L.x3_tab[t])))
-      return rc;
-  }
-  if ((rc = run_x3(bt, s))) return rc;
-  record_pack(packed, dims->precision);
-  return AVR_OK;
-}
-
-extern "C" int avr_field_bwd_packed_floats(const avr_field_dims* dims, int64_t* n_floats) {
-  Layout L;
-  BwdLayout LB;
-  const int rc = make_layout(dims, &L);
-  if (rc) return rc;
-  AVR_REQUIRE(n_floats, "avr_field_bwd_packed_floats: null output");
-  make_bwd_layout(dims, &LB);
-  *n_floats = LB.total;
-  return AVR_OK;
-}
-
-extern "C" int avr_field_pack_bwd(const avr_field_dims* dims, const avr_resnetfc_weights* w, float* packed_bwd,
-                                  void* stream) {
-  Layout L;
-  BwdLayout LB;
-  int rc = make_layout(dims, &L);
-  if (rc) return rc;
-  AVR_REQUIRE(w && packed_bwd, "avr_field_pack_bwd: null pointer");
-  make_bwd_layout(dims, &LB);
-  hipStream_t s = as_stream(stream);
-  unsigned* hdr = reinterpret_cast<unsigned*>(packed_bwd);
-  if (hipMemsetAsync(hdr, 0, 64 * sizeof(float), s) != hipSuccess) return fail(AVR_E_HIP, "avr_field_pack_bwd: memset");
-  const int H = dims->d_hidden, KC = H / 32, NT = H / 16;
-  X3PackBatch bt{};
-  for (int b = 0; b < dims->n_blocks; ++b) {
-    if ((rc = add_x3(bt, w->fc0_w[b], H, H, KC, NT, hdr + 2 + 2 * b, packed_bwd + LB.fc0t[b], true))) return rc;
-    if ((rc = add_x3(bt, w->fc1_w[b], H, H, KC, NT, hdr + 3 + 2 * b, packed_bwd + LB.fc1t[b], true))) return rc;
-  }
-  for (int b = 0; b < AVR_MAX_BLOCKS; ++b)
-    if (LB.lzt[b] >= 0 &&
-        (rc = add_x3(bt, w->lin_z_w[b], H, H, KC, NT, hdr + kBwdLinZHdr + b, packed_bwd + LB.lzt[b], true)))
-      return rc;
-  return run_x3(bt, s);
-}
-
-extern "C" int avr_field_train_sizes(const avr_field_dims* dims, int n_scenes, int64_t n_points, int64_t* act_floats,
-                                     int64_t* mask_words_out) {
-  Layout L;
-  const int rc = make_layout(dims, &L);
-  if (rc) return rc;
-  AVR_REQUIRE(n_scenes >= 1 && n_points >= 0 && act_floats && mask_words_out, "avr_field_train_sizes: bad argument");
-  const int64_t layers = 2 * dims->n_blocks + 1;
-  const int64_t blocks = n_scenes * ((n_points + kX3Samples - 1) / kX3Samples);
-  *act_floats = layers * n_scenes * n_points * dims->d_hidden;
-  *mask_words_out = layers * blocks * 4 * mask_words(dims->d_hidden / 64) * 64;
+  a->M = per_scene;
+  a->n_scenes = n_scenes;
+  a->blocks_per_scene = (per_scene + kX3Samples - 1) / kX3Samples;
+  a->table_scene_stride = (int64_t)(a->L.n_tables > 0 ? a->L.n_tables : 1) * a->table_stride;
   return AVR_OK;
 }
 
@@ -763,23 +364,14 @@ extern "C" int avr_field_fwd_points_train(const avr_field_dims* dims, const avr_
                                           int64_t act_rows, uint32_t* mask, uint32_t* act_max, float* z_feature,
                                           int ld_z, uint32_t* z_max, void* stream) {
   FieldArgs a{};
-  AVR_REQUIRE(views && n_scenes >= 1 && n_scenes <= AVR_MAX_SCENES,
-              "avr_field_fwd_points_train: 1..%d scenes per call", AVR_MAX_SCENES);
-  int rc = field_common(dims, views, packed, tables, &a);
+  int rc = field_batch(dims, views, n_scenes, packed, tables, &a, n_points, "avr_field_fwd_points_train");
   if (rc) return rc;
-  AVR_REQUIRE(dims->precision == AVR_FIELD_X3, "avr_field_fwd_points_train: the training path is x3 only");
   AVR_REQUIRE(!dims->bn && !dims->spade,
               "avr_field_fwd_points_train: BatchNorm nets train on avr_bn_layer_run, use_spade nets on the module path");
   AVR_REQUIRE(n_points >= 0, "avr_field_fwd_points_train: bad size");
   AVR_REQUIRE(n_points == 0 || (xyz && viewdirs && out && act && mask), "avr_field_fwd_points_train: null pointer");
   AVR_REQUIRE(act_rows >= n_scenes * n_points, "avr_field_fwd_points_train: act_rows < n_scenes * n_points");
-  for (int s = 0; s < n_scenes; ++s) {
-    AVR_REQUIRE(views[s].latent_h == views[0].latent_h && views[s].latent_w == views[0].latent_w,
-                "avr_field_fwd_points_train: scenes need latent maps of one size");
-    view_from_desc(&views[s], &a.views[s]);
-  }
   a.xyz = xyz; a.vd = viewdirs; a.n_samples = 1;
-  a.M = n_points;
   a.out = reinterpret_cast<float4*>(out);
   a.act = act;
   a.act_stride = act_rows * dims->d_hidden;
@@ -789,9 +381,6 @@ extern "C" int avr_field_fwd_points_train(const avr_field_dims* dims, const avr_
   a.zf = z_feature;
   a.zf_ld = ld_z;
   a.zf_max = z_max;
-  a.n_scenes = n_scenes;
-  a.blocks_per_scene = (n_points + kX3Samples - 1) / kX3Samples;
-  a.table_scene_stride = (int64_t)(a.L.n_tables > 0 ? a.L.n_tables : 1) * a.table_stride;
   if (a.M == 0) return AVR_OK;
   return dispatch_field_x3(dims->d_hidden, a, as_stream(stream));
 }
@@ -801,7 +390,7 @@ extern "C" int avr_field_bwd(const avr_field_dims* dims, const float* packed, co
                              const float* act, int64_t act_rows, float* grads, int64_t grads_rows,
                              uint32_t* grads_max, void* stream) {
   BwdArgs a{};
-  int rc = make_layout(dims, &a.L);
+  int rc = field_layout(dims, &a.L);
   if (rc) return rc;
   AVR_REQUIRE(dims->precision == AVR_FIELD_X3, "avr_field_bwd: the training path is x3 only");
   AVR_REQUIRE(!dims->bn && !dims->spade,
@@ -815,7 +404,7 @@ extern "C" int avr_field_bwd(const avr_field_dims* dims, const float* packed, co
   if (n_points == 0) return AVR_OK;
   AVR_REQUIRE(packed && packed_bwd && out && grad_out && mask && grads, "avr_field_bwd: null pointer");
   AVR_REQUIRE(grads_rows >= n_scenes * n_points, "avr_field_bwd: grads_rows < n_scenes * n_points");
-  make_bwd_layout(dims, &a.LB);
+  if ((rc = field_bwd_layout(dims, &a.LB))) return rc;
   a.packed = packed;
   a.packed_bwd = packed_bwd;
   a.n_blocks = dims->n_blocks;
@@ -834,7 +423,7 @@ extern "C" int avr_field_bwd(const avr_field_dims* dims, const float* packed, co
 extern "C" int avr_field_latent_table(const avr_field_dims* dims, const float* packed, const float* latent, int H,
                                       int W, float* table, void* stream) {
   Layout L;
-  int rc = make_layout(dims, &L);
+  int rc = field_layout(dims, &L);
   if (rc) return rc;
   AVR_REQUIRE(packed && latent && table, "avr_field_latent_table: null pointer");
   AVR_REQUIRE(H > 0 && W > 0, "avr_field_latent_table: bad latent size");
@@ -844,19 +433,15 @@ extern "C" int avr_field_latent_table(const avr_field_dims* dims, const float* p
   // AVR_FIELD_FP32: exact fp32 products (inference: computed once per latent map)
   if (dims->precision == AVR_FIELD_X3 && L.x3_tables)
     return dispatch_table_x3(packed, L, latent, H * W, dims->d_latent, dims->d_hidden, table, 1, s);
-  switch (dims->d_hidden) {
-    case 64: return launch_table<4>(packed, L, latent, H * W, L.n_tables, table, s);
-    case 128: return launch_table<8>(packed, L, latent, H * W, L.n_tables, table, s);
-    case 256: return launch_table<16>(packed, L, latent, H * W, L.n_tables, table, s);
-    case 512: return launch_table<32>(packed, L, latent, H * W, L.n_tables, table, s);
-  }
-  return fail(AVR_E_UNSUPPORTED, "field: d_hidden %d", dims->d_hidden);
+  return fp32_width(dims->d_hidden, [&](auto nt) {
+    return launch_table<decltype(nt)::value>(packed, L, latent, H * W, L.n_tables, table, s);
+  });
 }
 
 extern "C" int avr_field_latent_table_batch(const avr_field_dims* dims, const float* packed, const float* latent,
                                             int n_scenes, int H, int W, float* table, void* stream) {
   Layout L;
-  int rc = make_layout(dims, &L);
+  int rc = field_layout(dims, &L);
   if (rc) return rc;
   AVR_REQUIRE(n_scenes >= 1, "avr_field_latent_table_batch: n_scenes must be >= 1");
   AVR_REQUIRE(packed && latent && table, "avr_field_latent_table_batch: null pointer");
@@ -889,27 +474,6 @@ extern "C" int avr_field_fwd_rays(const avr_field_dims* dims, const avr_view_des
   a.out = reinterpret_cast<float4*>(out);
   if (a.M == 0) return AVR_OK;
   return dispatch_field(dims, a, as_stream(stream));
-}
-
-// Several scenes in one launch (x3 path): scene s's samples are rows s * per_scene .. of the inputs, its lin_z
-// tables at tables + s * max(n_tables, 1) * H*W * d_hidden (FusedField.tables_batch), its view views[s].
-static int field_batch(const avr_field_dims* dims, const avr_view_desc* views, int n_scenes, const float* packed,
-                       const float* tables, FieldArgs* a, int64_t per_scene, const char* what) {
-  AVR_REQUIRE(views && n_scenes >= 1 && n_scenes <= AVR_MAX_SCENES, "%s: 1..%d scenes per call", what,
-              AVR_MAX_SCENES);
-  AVR_REQUIRE(dims && dims->precision == AVR_FIELD_X3, "%s: the multi-scene launch is x3 only", what);
-  int rc = field_common(dims, views, packed, tables, a);
-  if (rc) return rc;
-  for (int s = 0; s < n_scenes; ++s) {
-    AVR_REQUIRE(views[s].latent_h == views[0].latent_h && views[s].latent_w == views[0].latent_w,
-                "%s: scenes need latent maps of one size", what);
-    view_from_desc(&views[s], &a->views[s]);
-  }
-  a->M = per_scene;
-  a->n_scenes = n_scenes;
-  a->blocks_per_scene = (per_scene + kX3Samples - 1) / kX3Samples;
-  a->table_scene_stride = (int64_t)(a->L.n_tables > 0 ? a->L.n_tables : 1) * a->table_stride;
-  return AVR_OK;
 }
 
 extern "C" int avr_field_fwd_rays_batch(const avr_field_dims* dims, const avr_view_desc* views, int n_scenes,

@@ -33,14 +33,12 @@ __device__ __forceinline__ floatx4 masked(const floatx4& v, const unsigned* mb, 
   return r;
 }
 
-// (8 waves, d_hidden 512: the masks are in the 4-wave layout -- wave w's tile 4 w + ft is tile 4 (w & 1) + ft of
-// 4-wave wave w >> 1, its words 2 (w & 1) + q there)
+// (8 waves, d_hidden 512: the masks are in the 4-wave layout's words, mask_words8)
 template <int FT, int NW>
 __device__ __forceinline__ void load_mask(unsigned (&mb)[mask_words(FT)], const unsigned* mask, int layer, int lane,
                                           int wid) {
   constexpr int MW = mask_words(FT);
-  const unsigned* mk = NW == 8 ? mask + ((((int64_t)layer * gridDim.x + blockIdx.x) * 4 + (wid >> 1)) * 4 +
-                                         2 * (wid & 1)) * 64 + lane
+  const unsigned* mk = NW == 8 ? mask_words8(mask, layer, wid) + lane
                                : mask + (((int64_t)layer * gridDim.x + blockIdx.x) * NW + wid) * MW * 64 + lane;
 #pragma unroll
   for (int q = 0; q < MW; ++q) mb[q] = mk[q * 64];
@@ -79,34 +77,19 @@ __device__ __forceinline__ void store_rows(float* G, const floatx4 (&v)[FT][4], 
     }
 }
 
-// G rows of `layer` copied out of the LDS operand by a GEMM side task (x3_gemm.h RowSideH): lane (g, j)
-// of wave w copies sample 16 w + j
-template <int HID>
-__device__ __forceinline__ RowSideH<HID> grad_side(const BwdArgs& a, int layer, float s_x, int64_t base, int64_t roff,
-                                                   int wid) {
-  RowSideH<HID> rs;
-  rs.template init<HID>(a.G + (int64_t)layer * a.g_stride + (roff + base) * HID, s_x, a.M - base, wid);
-  return rs;
-}
-
-template <int HID>
-__device__ __forceinline__ RowSide8<HID> grad_side8(const BwdArgs& a, int layer, float s_x, int64_t base, int64_t roff,
-                                                    int wid) {
-  RowSide8<HID> rs;
-  rs.init8(a.G + (int64_t)layer * a.g_stride + (roff + base) * HID, s_x, a.M - base, wid);
-  return rs;
-}
-
-// the K loop of one backward GEMM: 4 waves (gemm_x3 with the row side task) or 8 (gemm_x3_sg_side)
+// The K loop of one backward GEMM with its side task: the G rows of `layer` are copied out of the LDS operand
+// while the MFMAs run (x3_gemm.h: 4 waves RowSideH, lane (g, j) of wave w copies sample 16 w + j; 8 waves RowSide8)
 template <int FT, int NW, int HID>
 __device__ __forceinline__ void bwd_gemm(floatx4 (&acc)[FT][4], FragX3 (&A0)[FT], const uint4* W, const uint4* X16,
                                          int lane, const BwdArgs& a, int layer, float s_x, int64_t base, int64_t roff,
                                          int wid) {
   constexpr int KC = HID / 32, NTT = FT * NW;
+  std::conditional_t<NW == 8, RowSide8<HID>, RowSideH<HID>> rs;
+  rs.start(a.G + (int64_t)layer * a.g_stride + (roff + base) * HID, s_x, a.M - base, wid);
   if constexpr (NW == 8)
-    gemm_x3_sg_side<FT, true>(acc, A0, W, KC, 64 * NTT, X16, lane, grad_side8<HID>(a, layer, s_x, base, roff, wid));
+    gemm_x3_sg<FT, true, FT>(acc, A0, W, KC, 64 * NTT, X16, lane, rs);
   else
-    gemm_x3<FT, true, false>(acc, A0, W, KC, 64 * NTT, X16, lane, grad_side<HID>(a, layer, s_x, base, roff, wid));
+    gemm_x3<FT, true, false>(acc, A0, W, KC, 64 * NTT, X16, lane, rs);
 }
 
 template <int FT>
@@ -223,43 +206,21 @@ template <int FT, int NW, int ACT>
 static int launch_bwd(const BwdArgs& a, hipStream_t s) {
   constexpr int HID = 16 * FT * NW;
   const size_t shm = (size_t)(HID / 32) * 8192 + 64 + 4 * kX3MaxLayers;
-  static bool attr = false;
-  if (!attr) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&field_bwd_x3_kernel<FT, NW, ACT>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm) != hipSuccess)
-      return fail(AVR_E_HIP, "field_bwd_x3_kernel: cannot set dynamic LDS to %zu", shm);
-    attr = true;
-  }
-  const int64_t blocks = a.blocks_per_scene * a.n_scenes;
-  AVR_REQUIRE(blocks < (1ll << 31), "field backward: too many points");
-  field_bwd_x3_kernel<FT, NW, ACT><<<(unsigned)blocks, 64 * NW, shm, s>>>(a);
-  return check_launch("field_bwd_x3_kernel");
+  return launch_lds<field_bwd_x3_kernel<FT, NW, ACT>>("field_bwd_x3_kernel", "field backward: too many points",
+                                                      a.blocks_per_scene * a.n_scenes, 1, 1, 64 * NW, shm, shm, s, a);
 }
 
 // d_hidden 512, ReLU: 8 waves x 4 tiles, two waves per SIMD as the forward (AVR_X3_BWD_WAVES=4: the 4-wave
 // layout, A/B); Softplus keeps the 4-wave layout (its slopes come from the act rows)
-static int bwd_waves() {
-  const char* e = getenv("AVR_X3_BWD_WAVES");
-  return (e && atoi(e) == 4) ? 4 : 8;
-}
-
-template <int ACT>
-static int dispatch_bwd_act(int d_hidden, const BwdArgs& a, hipStream_t s) {
-  switch (d_hidden) {
-    case 64: return launch_bwd<1, 4, ACT>(a, s);
-    case 128: return launch_bwd<2, 4, ACT>(a, s);
-    case 256: return launch_bwd<4, 4, ACT>(a, s);
-    case 512:
-      if constexpr (ACT == 0) {
-        if (bwd_waves() == 8) return launch_bwd<4, 8, ACT>(a, s);
-      }
-      return launch_bwd<8, 4, ACT>(a, s);
-  }
-  return fail(AVR_E_UNSUPPORTED, "field backward: d_hidden %d", d_hidden);
-}
-
 int dispatch_field_bwd_x3(int d_hidden, const BwdArgs& a, hipStream_t s) {
-  return a.beta > 0.f ? dispatch_bwd_act<1>(d_hidden, a, s) : dispatch_bwd_act<0>(d_hidden, a, s);
+  const char* what = "field backward";
+  if (a.beta > 0.f)
+    return x3_width<4>(d_hidden, false, what, [&](auto ft, auto nw) {
+      return launch_bwd<decltype(ft)::value, decltype(nw)::value, 1>(a, s);
+    });
+  return x3_width<0>(d_hidden, env_eight_waves("AVR_X3_BWD_WAVES"), what, [&](auto ft, auto nw) {
+    return launch_bwd<decltype(ft)::value, decltype(nw)::value, 0>(a, s);
+  });
 }
 
 }  // namespace avr

@@ -1,7 +1,10 @@
-// Shared pieces of the radiance-field kernels (field.hip: fp32 MFMA path and
-// packing; field_x3.hip: split-fp16 MFMA path).
+// Shared pieces of the radiance-field kernels (field.hip: fp32 MFMA path and the
+// entry points; field_pack.hip: blob layouts and packing; field_x3.hip: split-fp16 MFMA path).
 #pragma once
 #include <math.h>
+#include <stdlib.h>
+
+#include <type_traits>
 
 #include "avr_common.h"
 
@@ -14,7 +17,6 @@ constexpr int kSPW = 16;         // fp32 path: samples per wave (MFMA column cou
 constexpr int kInTiles = 3;      // fp32 path: lin_in K = 42 features padded to 48
 constexpr int kX3Samples = 64;   // x3 path: samples per workgroup (4 MFMA column groups)
 constexpr int kX3InChunks = 2;   // x3 path: lin_in K padded to 64 = 2 chunks of 32
-constexpr int kPeSlots = 11;     // x3 prologue: PE entries per lane (6 * num_freqs <= 42)
 constexpr int kX3MaxLayers = 2 + 2 * AVR_MAX_BLOCKS;
 
 // Packed blob (floats). fp32 part: [t][ot][lane] float4 fragments for
@@ -57,6 +59,26 @@ constexpr int kBwdLinZHdr = AVR_BN_LAYER_LIN_Z_T;   // header words 34 .. 41
 // GEMM inputs, one bit per (feature, sample) a lane holds, bit
 // (ft * 4 + sg) * 4 + r; words [layer][workgroup][wave][word][lane].
 __host__ __device__ constexpr int mask_words(int FT) { return (FT * 16 + 31) / 32; }
+
+// The relu mask nibble of the 4 values y a lane holds of one (tile, sample group)
+__device__ __forceinline__ unsigned relu_nibble(const floatx4& y) {
+  return (y.x > 0.f ? 1u : 0u) | (y.y > 0.f ? 2u : 0u) | (y.z > 0.f ? 4u : 0u) | (y.w > 0.f ? 8u : 0u);
+}
+
+// bits |= the nibble of (tile ft, sample group sg)
+template <int MW>
+__device__ __forceinline__ void set_mask_bits(unsigned (&bits)[MW], const floatx4& y, int ft, int sg) {
+  const int idx = (ft * 4 + sg) * 4;
+  bits[idx >> 5] |= relu_nibble(y) << (idx & 31);
+}
+
+// 8-wave layout at d_hidden 512 (FT 4): wave wid's two mask words of `layer` (lane 0; word q at + 64 q). The bits
+// live in the 4-wave layout's words: the 16-feature tile 4 wid + ft is tile 4 (wid & 1) + ft of 4-wave wave
+// wid >> 1, word 2 (wid & 1) + ft / 2 there.
+template <typename U>
+__device__ __forceinline__ U* mask_words8(U* mask, int layer, int wid) {
+  return mask + ((((int64_t)layer * gridDim.x + blockIdx.x) * 4 + (wid >> 1)) * 4 + 2 * (wid & 1)) * 64;
+}
 
 struct View {
   float R[9], t[3];
@@ -293,11 +315,41 @@ __device__ __forceinline__ float pow2_scale_for(float maxabs) {
   return ldexpf(1.0f, k < -60 ? -60 : (k > 60 ? 60 : k));
 }
 
+// d_hidden -> (FT feature tiles per wave, NW waves) of the x3 kernels: f(FT, NW) is called with integral
+// constants. d_hidden 512 has two layouts, 8 waves x 4 tiles and 4 waves x 8 tiles: W512 = 8 or 4 instantiates
+// only that one, W512 = 0 both, chosen per call by `eight`.
+template <int W512, typename F>
+int x3_width(int d_hidden, bool eight, const char* what, F f) {
+  using std::integral_constant;
+  switch (d_hidden) {
+    case 64: return f(integral_constant<int, 1>{}, integral_constant<int, 4>{});
+    case 128: return f(integral_constant<int, 2>{}, integral_constant<int, 4>{});
+    case 256: return f(integral_constant<int, 4>{}, integral_constant<int, 4>{});
+    case 512:
+      if constexpr (W512 != 4) {
+        if (W512 == 8 || eight) return f(integral_constant<int, 4>{}, integral_constant<int, 8>{});
+      }
+      if constexpr (W512 != 8) return f(integral_constant<int, 8>{}, integral_constant<int, 4>{});
+  }
+  return fail(AVR_E_UNSUPPORTED, "%s: d_hidden %d", what, d_hidden);
+}
+
+// The layout switches AVR_X3_WAVES / AVR_X3_SAVE_WAVES / AVR_X3_BWD_WAVES (diagnostics, A/B): 4 selects the
+// 4-wave layout at d_hidden 512, anything else the 8-wave one. Read per launch so a test can switch layouts in
+// one process.
+inline bool env_eight_waves(const char* name) {
+  const char* e = getenv(name);
+  return !(e && atoi(e) == 4);
+}
+
 int dispatch_field_x3(int d_hidden, const FieldArgs& a, hipStream_t s);
-// The packed blob's layout for dims (field.hip make_layout / make_bwd_layout), for the kernels of other units
-// (bn_train.hip: the layer-by-layer BatchNorm training GEMMs read the same fragments).
+// The packed blobs' layouts for dims (field_pack.hip; both check dims), for the entry points and the kernels of
+// other units (bn_train.hip: the layer-by-layer BatchNorm training GEMMs read the same fragments).
 int field_layout(const avr_field_dims* d, Layout* L);
 int field_bwd_layout(const avr_field_dims* d, BwdLayout* LB);
+// The precision (AVR_FIELD_*) the blob at p was packed for by avr_field_pack, -1: not packed by this library
+// instance (or evicted from the tag table)
+int packed_precision(const float* p);
 // lin_z / scale_z tables on the x3 GEMM (L.x3_tables): table[t][texel][d_hidden], t < L.n_tables, for
 // n_scenes latent maps (stride d_latent * HW) into tables back to back (stride max(n_tables, 1) * HW * d_hidden)
 int dispatch_table_x3(const float* packed, const Layout& L, const float* latent, int HW, int d_latent, int d_hidden,

@@ -21,8 +21,6 @@
 // Accumulators stay in their scaled domain between layers (no unscale pass),
 // and the bilinear lin_z gather for block b+1 streams in during block b's fc_0
 // MFMAs (issued one K-chunk ahead, added into the residual).
-#include <stdlib.h>
-
 #include "x3_gemm.h"
 
 namespace avr {
@@ -121,15 +119,6 @@ __device__ __forceinline__ void stage_rows(char* stage, const float* __restrict_
 
 typedef __attribute__((address_space(3))) char lds_char;
 
-template <int FT, bool ZERO, bool TWO>
-__device__ __forceinline__ void gemm(floatx4 (&acc)[FT][4], FragX3 (&A0)[FT], const uint4* __restrict__ W, int KC,
-                                     int cstride, const uint4* X16, int lane) {
-  if constexpr (TWO)
-    gemm_x3_sg<FT, ZERO, FT>(acc, A0, W, KC, cstride, X16, lane);
-  else
-    gemm_x3<FT, ZERO, false>(acc, A0, W, KC, cstride, X16, lane);
-}
-
 // h += S * sum_c w_c * row(slot_c) over the corners whose slot is in [lo, lo+n).
 // PREP: also v = act(h * f) and the running max of max(0, h * f) for the next
 // publish (the fc_0 input of the block), from the same register read of h.
@@ -221,63 +210,11 @@ __device__ __forceinline__ void save_layer(const FieldArgs& a, int layer, const 
       const int64_t m = base + 16 * sg + j;
       if (m < a.M) __builtin_nontemporal_store(x, reinterpret_cast<floatx4*>(act + m * HID + 16 * (FT * wid + ft) + 4 * g));
       const int idx = (ft * 4 + sg) * 4;
-      const unsigned nib = (x.x > 0.f ? 1u : 0u) | (x.y > 0.f ? 2u : 0u) | (x.z > 0.f ? 4u : 0u) | (x.w > 0.f ? 8u : 0u);
-      bits[idx >> 5] |= nib << (idx & 31);
+      bits[idx >> 5] |= relu_nibble(x) << (idx & 31);
     }
   unsigned* mk = a.mask + (((int64_t)layer * gridDim.x + blockIdx.x) * NW + wid) * MW * 64 + lane;
 #pragma unroll
   for (int q = 0; q < MW; ++q) mk[q * 64] = bits[q];
-}
-
-// Training forward on the 8-wave layout (d_hidden 512: FT 4 x NW 8, two waves per SIMD as in inference; the
-// 4-wave layout's materialised layer input v does not fit its 256 registers): the two-pass publish of
-// act(acc * f [+ b]) also stores each value as its act row and its relu mask bit, the bits in the 4-wave
-// layout's mask words (field_bwd_x3_kernel<8, 4> reads them: the 16-feature tile 4 wid + ft is tile
-// 4 (wid & 1) + ft of 4-wave wave wid >> 1, word 2 (wid & 1) + ft / 2 there); the workgroup's max goes to *lmax.
-template <int FT, int NW, bool BIAS>
-__device__ __forceinline__ float publish_affine_save(uint4* X16, const floatx4 (&acc)[FT][4], float f,
-                                                     const floatx4 (&bv)[FT], float mx, float* red, int wid, int lane,
-                                                     int g, int j, const FieldArgs& a, int layer, int64_t base,
-                                                     int64_t roff, float* lmax) {
-  static_assert(FT == 4 && NW == 8, "8-wave training forward: d_hidden 512");
-  constexpr int HID = 16 * FT * NW;
-  if (lane == 0) red[wid] = mx;
-  lds_barrier();
-  const float m = red_max<NW>(red);
-  if (wid == 0 && lane == 0) *lmax = m;
-  const float s_x = pow2_scale_for(m);
-  char* xb = reinterpret_cast<char*>(X16);
-  // the tile's rows from a wave-uniform base, 32-bit lane offsets recomputed here from an opaque lane id (hoisted
-  // out of the block loop, the per-row addresses would stay live across it and spill)
-  int ln = lane;
-  asm volatile("" : "+v"(ln));
-  g = ln >> 4;
-  j = ln & 15;
-  float* act = a.act + (int64_t)layer * a.act_stride + (roff + base) * HID;
-  const int nval = a.M - base < 64 ? (int)(a.M - base) : 64;
-  unsigned bits[2] = {0u, 0u};
-#pragma unroll
-  for (int ft = 0; ft < FT; ++ft) {
-    const int ftg = FT * wid + ft;
-#pragma unroll
-    for (int sg = 0; sg < 4; ++sg) {
-      const floatx4 y = relu_affine<BIAS, 0>(acc[ft][sg], f, bv[ft]);
-      uint2 hi, lo;
-      split4(y, s_x, hi, lo);
-      const int s = 16 * sg + j;
-      *reinterpret_cast<uint2*>(xb + xidx(ftg >> 1, 0, g, s) * 16 + (ftg & 1) * 8) = hi;
-      *reinterpret_cast<uint2*>(xb + xidx(ftg >> 1, 1, g, s) * 16 + (ftg & 1) * 8) = lo;
-      if (s < nval) __builtin_nontemporal_store(y, reinterpret_cast<floatx4*>(act + (unsigned)(s * HID + 16 * ftg + 4 * g)));
-      const int idx = (ft * 4 + sg) * 4;
-      bits[idx >> 5] |= ((y.x > 0.f ? 1u : 0u) | (y.y > 0.f ? 2u : 0u) | (y.z > 0.f ? 4u : 0u) | (y.w > 0.f ? 8u : 0u))
-                        << (idx & 31);
-    }
-  }
-  unsigned* mk = a.mask + ((((int64_t)layer * gridDim.x + blockIdx.x) * 4 + (wid >> 1)) * 4 + 2 * (wid & 1)) * 64 + ln;
-  mk[0] = bits[0];
-  mk[64] = bits[1];
-  lds_barrier();
-  return s_x;
 }
 
 // Work split: NW waves (4: one per SIMD; 8: two per SIMD, which doubles the
@@ -455,8 +392,6 @@ __global__ void __launch_bounds__(64 * NW, 1) field_x3_kernel(FieldArgs a) {
       for (int sg = 0; sg < 4; ++sg) h[ft][sg] = b * S_h;
     }
     AVR_STAMP(3);
-    // 8 waves: stage rows of the next lin_z table that are already in flight
-    // ([p0, p1), issued while the preceding GEMM still read other parts of X)
     // 8 waves: block 0's lin_z stage rows that do not overlap lin_in's X are DMA'd before the lin_in GEMM
     constexpr bool PRE0 = TWO;
     if (PRE0 && a.n_lin_z > 0 && D <= P::CAP && D > P::IN_ROWS0) {
@@ -647,54 +582,42 @@ __global__ void __launch_bounds__(64 * NW, 1) field_x3_kernel(FieldArgs a) {
     // workgroup's max through red
     unsigned sbits[2] = {0u, 0u};
     const int lout = 2 * a.n_blocks;
+    float* sact = nullptr;
+    int snval = 0;
     if constexpr (SAVE) {
-      float* sact = a.act + (int64_t)lout * a.act_stride + (roff + base) * HID;
-      const int snval = a.M - base < 64 ? (int)(a.M - base) : 64;
+      sact = a.act + (int64_t)lout * a.act_stride + (roff + base) * HID;
+      snval = a.M - base < 64 ? (int)(a.M - base) : 64;
+    }
 #pragma unroll
-      for (int sg = 0; sg < 4; ++sg) {
-        part[sg] = floatx4{0.f, 0.f, 0.f, 0.f};
+    for (int sg = 0; sg < 4; ++sg) {
+      part[sg] = floatx4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-        for (int cc = 0; cc < 2; ++cc) {
-          uint2 h0, l0, h1, l1;
-          const floatx4 y0 = relu_affine<false, ACT>(h[2 * cc][sg], f, bz[0], beta);
-          const floatx4 y1 = relu_affine<false, ACT>(h[2 * cc + 1][sg], f, bz[0], beta);
-          if constexpr (SAVE) {
-            const int srow = 16 * sg + j;
+      for (int cc = 0; cc < 2; ++cc) {
+        // (statement order is scheduling input: with SAVE both values are formed ahead of their stores, without
+        // it each right at its split)
+        uint2 h0, l0, h1, l1;
+        const floatx4 y0 = relu_affine<false, ACT>(h[2 * cc][sg], f, bz[0], beta);
+        floatx4 y1;
+        if constexpr (SAVE) {
+          y1 = relu_affine<false, ACT>(h[2 * cc + 1][sg], f, bz[0], beta);
+          const int srow = 16 * sg + j;
 #pragma unroll
-            for (int q = 0; q < 2; ++q) {
-              const floatx4 y = q ? y1 : y0;
-              const int ft = 2 * cc + q, ftg = FT * wid + ft;
-              if (srow < snval)
-                __builtin_nontemporal_store(y, reinterpret_cast<floatx4*>(sact + (unsigned)(srow * HID + 16 * ftg + 4 * g)));
-              const int idx = (ft * 4 + sg) * 4;
-              sbits[idx >> 5] |= ((y.x > 0.f ? 1u : 0u) | (y.y > 0.f ? 2u : 0u) | (y.z > 0.f ? 4u : 0u) |
-                                  (y.w > 0.f ? 8u : 0u)) << (idx & 31);
-            }
+          for (int q = 0; q < 2; ++q) {
+            const floatx4 y = q ? y1 : y0;
+            const int ft = 2 * cc + q, ftg = FT * wid + ft;
+            if (srow < snval)
+              __builtin_nontemporal_store(y, reinterpret_cast<floatx4*>(sact + (unsigned)(srow * HID + 16 * ftg + 4 * g)));
+            set_mask_bits(sbits, y, ft, sg);
           }
-          split4(y0, s_w, h0, l0);
-          split4(y1, s_w, h1, l1);
-          const half8 bh = __builtin_bit_cast(half8, make_uint4(h0.x, h0.y, h1.x, h1.y));
-          const half8 bl = __builtin_bit_cast(half8, make_uint4(l0.x, l0.y, l1.x, l1.y));
-          part[sg] = mfma32h(Aw[cc].hi, bh, part[sg]);
-          part[sg] = mfma32h(Aw[cc].hi, bl, part[sg]);
-          part[sg] = mfma32h(Aw[cc].lo, bh, part[sg]);
         }
-      }
-    } else {
-#pragma unroll
-      for (int sg = 0; sg < 4; ++sg) {
-        part[sg] = floatx4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int cc = 0; cc < 2; ++cc) {
-          uint2 h0, l0, h1, l1;
-          split4(relu_affine<false, ACT>(h[2 * cc][sg], f, bz[0], beta), s_w, h0, l0);
-          split4(relu_affine<false, ACT>(h[2 * cc + 1][sg], f, bz[0], beta), s_w, h1, l1);
-          const half8 bh = __builtin_bit_cast(half8, make_uint4(h0.x, h0.y, h1.x, h1.y));
-          const half8 bl = __builtin_bit_cast(half8, make_uint4(l0.x, l0.y, l1.x, l1.y));
-          part[sg] = mfma32h(Aw[cc].hi, bh, part[sg]);
-          part[sg] = mfma32h(Aw[cc].hi, bl, part[sg]);
-          part[sg] = mfma32h(Aw[cc].lo, bh, part[sg]);
-        }
+        split4(y0, s_w, h0, l0);
+        if constexpr (!SAVE) y1 = relu_affine<false, ACT>(h[2 * cc + 1][sg], f, bz[0], beta);
+        split4(y1, s_w, h1, l1);
+        const half8 bh = __builtin_bit_cast(half8, make_uint4(h0.x, h0.y, h1.x, h1.y));
+        const half8 bl = __builtin_bit_cast(half8, make_uint4(l0.x, l0.y, l1.x, l1.y));
+        part[sg] = mfma32h(Aw[cc].hi, bh, part[sg]);
+        part[sg] = mfma32h(Aw[cc].hi, bl, part[sg]);
+        part[sg] = mfma32h(Aw[cc].lo, bh, part[sg]);
       }
     }
     const float un = 1.0f / (layer_scale(a.packed, L, 1) * s_w);
@@ -707,8 +630,7 @@ __global__ void __launch_bounds__(64 * NW, 1) field_x3_kernel(FieldArgs a) {
       }
     }
     if constexpr (SAVE) {
-      unsigned* mk = a.mask + ((((int64_t)lout * gridDim.x + blockIdx.x) * 4 + (wid >> 1)) * 4 + 2 * (wid & 1)) * 64 +
-                     lane;
+      unsigned* mk = mask_words8(a.mask, lout, wid) + lane;
       mk[0] = sbits[0];
       mk[64] = sbits[1];
       if (lane == 0) red[wid] = mxw;
@@ -746,14 +668,9 @@ __global__ void __launch_bounds__(64 * NW, 1) field_x3_kernel(FieldArgs a) {
 #pragma unroll
     for (int c = 0; c < KC / 4; ++c) Ao[c] = load_frag(wo + (wlo + 2 * 64 * c));
   }
-  if constexpr (TWO) {
-    mx = act_bound<ACT>(max_relu_affine<FT, false>(h, 1.0f / S_h, bz), beta);
-    s_x = publish_affine<FT, NW, false, ACT>(X16, h, 1.0f / S_h, bz, mx, red, wid, lane, g, j, beta);
-  } else {
-    mx = act_bound<ACT>(prep_input<FT, false, ACT>(v, h, 1.0f / S_h, nullptr, wid, g, beta), beta);
-    if (SAVE) save_layer<FT, NW>(a, 2 * a.n_blocks, v, base, roff, wid, g, j, lane);
-    s_x = publish<FT, NW>(X16, v, mx, red, wid, lane, g, j, SAVE ? &tail->lmax[2 * a.n_blocks] : nullptr);
-  }
+  mx = act_bound<ACT>(prep_input<FT, false, ACT>(v, h, 1.0f / S_h, nullptr, wid, g, beta), beta);
+  if (SAVE) save_layer<FT, NW>(a, 2 * a.n_blocks, v, base, roff, wid, g, j, lane);
+  s_x = publish<FT, NW>(X16, v, mx, red, wid, lane, g, j, SAVE ? &tail->lmax[2 * a.n_blocks] : nullptr);
   if (wid < 4) {
 #pragma unroll
     for (int c = KC / 4; c < KC; ++c) Ao[c] = load_frag(wo + (wlo + 2 * 64 * c));
@@ -871,19 +788,12 @@ __global__ void __launch_bounds__(64 * NW, 1) table_x3_kernel(const float* __res
 template <int FT, int NW, bool ALL>
 static int launch_table_x3_k(const float* packed, const Layout& L, const float* latent, int HW, int d_latent,
                              float* table, int n_scenes, hipStream_t s) {
-  const size_t shm = (size_t)(d_latent / 32) * 8192 + 64;
-  static bool attr = false;
-  if (!attr) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&table_x3_kernel<FT, NW, ALL>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, 4 * 8192 * 4 + 64) != hipSuccess)
-      return fail(AVR_E_HIP, "table_x3_kernel: cannot set dynamic LDS");
-    attr = true;
-  }
-  const dim3 grid((unsigned)((HW + kX3Samples - 1) / kX3Samples), ALL ? 1u : (unsigned)L.n_tables, (unsigned)n_scenes);
+  const size_t shm = (size_t)(d_latent / 32) * 8192 + 64;   // at most d_latent 512 (dispatch_table_x3)
   const int64_t tab_stride = (int64_t)(L.n_tables > 0 ? L.n_tables : 1) * HW * (16 * FT * NW);
-  table_x3_kernel<FT, NW, ALL><<<grid, 64 * NW, shm, s>>>(packed, L, latent, HW, d_latent, table,
-                                                          (int64_t)d_latent * HW, tab_stride);
-  return check_launch("table_x3_kernel");
+  return launch_lds<table_x3_kernel<FT, NW, ALL>>("table_x3_kernel", "table x3: too many texels",
+                                                  (HW + kX3Samples - 1) / kX3Samples, ALL ? 1u : (unsigned)L.n_tables,
+                                                  (unsigned)n_scenes, 64 * NW, shm, 4 * 8192 * 4 + 64, s, packed, L,
+                                                  latent, HW, d_latent, table, (int64_t)d_latent * HW, tab_stride);
 }
 
 // every table per workgroup once the texel blocks alone give a workgroup to each CU (AVR_TABLE_ALL=0|1 forces
@@ -894,105 +804,59 @@ static bool table_all(int64_t blocks, int n_tables) {
   return n_tables > 1 && blocks >= 256;
 }
 
-template <int FT, int NW>
-static int launch_table_x3(const float* packed, const Layout& L, const float* latent, int HW, int d_latent,
-                           float* table, int n_scenes, hipStream_t s) {
-  const int64_t blocks = (int64_t)((HW + kX3Samples - 1) / kX3Samples) * n_scenes;
-  if (table_all(blocks, L.n_tables))
-    return launch_table_x3_k<FT, NW, true>(packed, L, latent, HW, d_latent, table, n_scenes, s);
-  return launch_table_x3_k<FT, NW, false>(packed, L, latent, HW, d_latent, table, n_scenes, s);
-}
-
 int dispatch_table_x3(const float* packed, const Layout& L, const float* latent, int HW, int d_latent, int d_hidden,
                       float* table, int n_scenes, hipStream_t s) {
   AVR_REQUIRE(L.x3_tables && d_latent % 64 == 0 && d_latent <= 512, "table x3: d_latent %d", d_latent);
-  switch (d_hidden) {
-    case 64: return launch_table_x3<1, 4>(packed, L, latent, HW, d_latent, table, n_scenes, s);
-    case 128: return launch_table_x3<2, 4>(packed, L, latent, HW, d_latent, table, n_scenes, s);
-    case 256: return launch_table_x3<4, 4>(packed, L, latent, HW, d_latent, table, n_scenes, s);
-    case 512: return launch_table_x3<4, 8>(packed, L, latent, HW, d_latent, table, n_scenes, s);
-  }
-  return fail(AVR_E_UNSUPPORTED, "table x3: d_hidden %d", d_hidden);
+  const int64_t blocks = (int64_t)((HW + kX3Samples - 1) / kX3Samples) * n_scenes;
+  const bool all = table_all(blocks, L.n_tables);
+  return x3_width<8>(d_hidden, true, "table x3", [&](auto ft, auto nw) {
+    constexpr int FT = decltype(ft)::value, NW = decltype(nw)::value;
+    return all ? launch_table_x3_k<FT, NW, true>(packed, L, latent, HW, d_latent, table, n_scenes, s)
+               : launch_table_x3_k<FT, NW, false>(packed, L, latent, HW, d_latent, table, n_scenes, s);
+  });
 }
 
 template <int FT, int NW, bool SAVE, bool BN = false, bool SPADE = false, int ACT = 0>
 static int launch_x3(const FieldArgs& a, hipStream_t s) {
   const size_t shm = LdsPlan<16 * FT * NW>::BYTES;
-  static bool attr = false;
-  if (!attr) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&field_x3_kernel<FT, NW, SAVE, BN, SPADE, ACT>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm) != hipSuccess)
-      return fail(AVR_E_HIP, "field_x3_kernel: cannot set dynamic LDS to %zu", shm);
-    attr = true;
-  }
   const int64_t blocks = (SAVE || a.n_scenes > 1) ? a.blocks_per_scene * a.n_scenes
                                                   : (a.M + kX3Samples - 1) / kX3Samples;
-  AVR_REQUIRE(blocks < (1ll << 31), "field: too many points");
-  field_x3_kernel<FT, NW, SAVE, BN, SPADE, ACT><<<(unsigned)blocks, 64 * NW, shm, s>>>(a);
-  return check_launch("field_x3_kernel");
+  return launch_lds<field_x3_kernel<FT, NW, SAVE, BN, SPADE, ACT>>("field_x3_kernel", "field: too many points",
+                                                                   blocks, 1, 1, 64 * NW, shm, shm, s, a);
 }
 
-// AVR_X3_WAVES (diagnostics), read per launch so a test can switch layouts in one process
-static int x3_waves() {
-  const char* e = getenv("AVR_X3_WAVES");
-  return (e && atoi(e) == 4) ? 4 : 8;
-}
-
-static int save_waves() {
-  const char* e = getenv("AVR_X3_SAVE_WAVES");
-  return (e && atoi(e) == 4) ? 4 : 8;
-}
-
+// d_hidden 512 runs 8 waves x 4 tiles where the variant has that layout (inference: +2.7-4.7 % over the 4-wave
+// layout on the same box); AVR_X3_WAVES=4 (inference) and AVR_X3_SAVE_WAVES=4 (training forward) select the
+// 4-wave layout where both exist (diagnostics, A/B).
 int dispatch_field_x3(int d_hidden, const FieldArgs& a, hipStream_t s) {
-  // inference at d_hidden 512: 8 waves x 4 tiles (+2.7-4.7 % over the 4-wave layout on the same box);
-  // AVR_X3_WAVES=4 selects the 4-wave layout (diagnostics)
+  const char* what = "field x3";
   if (a.L.bn) {   // eval-mode BatchNorm (inference only)
     AVR_REQUIRE(!a.act, "field x3: BatchNorm nets train on the module path");
-    switch (d_hidden) {
-      case 64: return launch_x3<1, 4, false, true>(a, s);
-      case 128: return launch_x3<2, 4, false, true>(a, s);
-      case 256: return launch_x3<4, 4, false, true>(a, s);
-      case 512: return x3_waves() == 8 ? launch_x3<4, 8, false, true>(a, s) : launch_x3<8, 4, false, true>(a, s);
-    }
-    return fail(AVR_E_UNSUPPORTED, "field x3: d_hidden %d", d_hidden);
+    return x3_width<0>(d_hidden, env_eight_waves("AVR_X3_WAVES"), what, [&](auto ft, auto nw) {
+      return launch_x3<decltype(ft)::value, decltype(nw)::value, false, true>(a, s);
+    });
   }
-  if (a.beta > 0.f && !a.L.spade && a.act) {   // Softplus training forward (4-wave SAVE layout, ABI 11)
-    switch (d_hidden) {
-      case 64: return launch_x3<1, 4, true, false, false, 1>(a, s);
-      case 128: return launch_x3<2, 4, true, false, false, 1>(a, s);
-      case 256: return launch_x3<4, 4, true, false, false, 1>(a, s);
-      case 512: return launch_x3<8, 4, true, false, false, 1>(a, s);
-    }
-    return fail(AVR_E_UNSUPPORTED, "field x3: d_hidden %d", d_hidden);
-  }
+  if (a.beta > 0.f && !a.L.spade && a.act)   // Softplus training forward (4-wave SAVE layout, ABI 11)
+    return x3_width<4>(d_hidden, false, what, [&](auto ft, auto nw) {
+      return launch_x3<decltype(ft)::value, decltype(nw)::value, true, false, false, 1>(a, s);
+    });
   if (a.L.spade || a.beta > 0.f) {   // use_spade and / or Softplus (inference)
     AVR_REQUIRE(!a.act, "field x3: use_spade nets train on the module path");
-    const int v = (a.L.spade ? 1 : 0) | (a.beta > 0.f ? 2 : 0);
-#define AVR_X3_OPT(FT, NW)                                      \
-  switch (v) {                                                  \
-    case 1: return launch_x3<FT, NW, false, false, true, 0>(a, s);  \
-    case 2: return launch_x3<FT, NW, false, false, false, 1>(a, s); \
-    default: return launch_x3<FT, NW, false, false, true, 1>(a, s); \
+    return x3_width<8>(d_hidden, true, what, [&](auto ft, auto nw) {
+      constexpr int FT = decltype(ft)::value, NW = decltype(nw)::value;
+      // (Softplus instantiations in this order: the compiler's inlining of the math library into them depends on it)
+      if (!(a.beta > 0.f)) return launch_x3<FT, NW, false, false, true, 0>(a, s);
+      if (!a.L.spade) return launch_x3<FT, NW, false, false, false, 1>(a, s);
+      return launch_x3<FT, NW, false, false, true, 1>(a, s);
+    });
   }
-    switch (d_hidden) {
-      case 64: AVR_X3_OPT(1, 4)
-      case 128: AVR_X3_OPT(2, 4)
-      case 256: AVR_X3_OPT(4, 4)
-      case 512: AVR_X3_OPT(4, 8)
-    }
-#undef AVR_X3_OPT
-    return fail(AVR_E_UNSUPPORTED, "field x3: d_hidden %d", d_hidden);
-  }
-  if (d_hidden == 512 && !a.act && x3_waves() == 8) return launch_x3<4, 8, false>(a, s);
-  // training forward at d_hidden 512: the 8-wave layout too (AVR_X3_SAVE_WAVES=4: the 4-wave one, A/B)
-  if (d_hidden == 512 && a.act && save_waves() == 8) return launch_x3<4, 8, true>(a, s);
-  switch (d_hidden) {
-    case 64: return a.act ? launch_x3<1, 4, true>(a, s) : launch_x3<1, 4, false>(a, s);
-    case 128: return a.act ? launch_x3<2, 4, true>(a, s) : launch_x3<2, 4, false>(a, s);
-    case 256: return a.act ? launch_x3<4, 4, true>(a, s) : launch_x3<4, 4, false>(a, s);
-    case 512: return a.act ? launch_x3<8, 4, true>(a, s) : launch_x3<8, 4, false>(a, s);
-  }
-  return fail(AVR_E_UNSUPPORTED, "field x3: d_hidden %d", d_hidden);
+  if (a.act)   // training forward
+    return x3_width<0>(d_hidden, env_eight_waves("AVR_X3_SAVE_WAVES"), what, [&](auto ft, auto nw) {
+      return launch_x3<decltype(ft)::value, decltype(nw)::value, true>(a, s);
+    });
+  return x3_width<0>(d_hidden, env_eight_waves("AVR_X3_WAVES"), what, [&](auto ft, auto nw) {
+    return launch_x3<decltype(ft)::value, decltype(nw)::value, false>(a, s);
+  });
 }
 
 }  // namespace avr

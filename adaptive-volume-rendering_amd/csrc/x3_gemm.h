@@ -112,6 +112,9 @@ struct RowSide {
 
 template <int HID>
 struct RowSideH : RowSide {
+  __device__ __forceinline__ void start(float* rows0, float s_x, int64_t nrows, int w) {
+    init<HID>(rows0, s_x, nrows, w);
+  }
   __device__ __forceinline__ void store(int c) { store_hid<HID>(c); }
 };
 
@@ -211,68 +214,19 @@ __device__ __forceinline__ void gemm_x3(floatx4 (&acc)[FT][4], FragX3 (&A0)[FT],
 // 8-wave variant of the K-chunk loop (256 registers per wave): sample groups
 // outermost, so only the current and the next B fragment pair are resident
 // (16 registers instead of 32); the next chunk's A fragment of tile sg loads
-// during sample group sg (FT == 4: one tile per group).
-template <int FT, bool ZERO>
+// during sample group sg (FT == 4: one tile per group). The side task (the
+// backward chain's G rows, RowSide8) reads its slots of chunk c in sample
+// group 0 and stores its rows in sample group 2.
+template <int FT, bool ZERO, typename Side = NoSide>
 __device__ __forceinline__ void chunk_step_sg(floatx4 (&acc)[FT][4], const FragX3 (&A)[FT], FragX3 (&An)[FT],
                                               const uint4* __restrict__ wn, unsigned lo, BPair& B, const uint4* X16,
-                                              int c, int cn, int g, int j) {
-  static_assert(FT == 4, "one next-chunk tile per sample group");
-#pragma unroll
-  for (int sg = 0; sg < 4; ++sg) {
-    const BPair Bn = sg < 3 ? read_b(X16, c, sg + 1, g, j) : read_b(X16, cn, 0, g, j);
-    An[sg] = load_frag(wn + (lo + 2 * 64 * sg));   // wave-uniform base + 32-bit lane offset
-#pragma unroll
-    for (int ft = 0; ft < FT; ++ft) {
-      acc[ft][sg] = mfma32h(A[ft].hi, B.hi, ZERO ? floatx4{0.f, 0.f, 0.f, 0.f} : acc[ft][sg]);
-      acc[ft][sg] = mfma32h(A[ft].hi, B.lo, acc[ft][sg]);
-      acc[ft][sg] = mfma32h(A[ft].lo, B.hi, acc[ft][sg]);
-    }
-    __builtin_amdgcn_sched_group_barrier(0x008, 4, 0);
-    __builtin_amdgcn_sched_group_barrier(0x020, 2, 0);
-    __builtin_amdgcn_sched_group_barrier(0x008, 4, 0);
-    __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
-    __builtin_amdgcn_sched_group_barrier(0x008, 4, 0);
-    __builtin_amdgcn_sched_barrier(0);
-    B = Bn;
-  }
-}
-
-// A0 holds chunk 0's first NPF tiles (prefetch_a<FT, NPF>). No barrier in the
-// loop: the two waves of a SIMD drift apart by priority (field_x3_kernel).
-template <int FT, bool ZERO, int NPF = FT>
-__device__ __forceinline__ void gemm_x3_sg(floatx4 (&acc)[FT][4], FragX3 (&A0)[FT], const uint4* __restrict__ W,
-                                           int KC, int cstride, const uint4* X16, int lane) {
-  const int g = lane >> 4, j = lane & 15;
-  const unsigned lo = lane;          // W (wave-uniform) + lo: this lane's fragment
-  FragX3 A1[FT];
-#pragma unroll
-  for (int ft = NPF; ft < FT; ++ft) A0[ft] = load_frag(W + (lo + 2 * 64 * ft));
-  BPair B = read_b(X16, 0, 0, g, j);
-  __builtin_amdgcn_sched_barrier(0);
-  for (int c = 0; c < KC; c += 2) {
-    const int c2 = c + 2 < KC ? c + 2 : c + 1;
-    const uint4* w1 = W + (int64_t)2 * (c + 1) * cstride;
-    const uint4* w2 = W + (int64_t)2 * c2 * cstride;
-    if (ZERO && c == 0)
-      chunk_step_sg<FT, true>(acc, A0, A1, w1, lo, B, X16, c, c + 1, g, j);
-    else
-      chunk_step_sg<FT, false>(acc, A0, A1, w1, lo, B, X16, c, c + 1, g, j);
-    chunk_step_sg<FT, false>(acc, A1, A0, w2, lo, B, X16, c + 1, c2, g, j);
-  }
-}
-
-// The 8-wave K loop with a side task (the backward chain's G rows, RowSide8): chunk_step_sg plus the task's LDS
-// read of chunk c in sample group 0 and its row stores in sample group 2.
-template <int FT, bool ZERO, typename Side>
-__device__ __forceinline__ void chunk_step_sg_side(floatx4 (&acc)[FT][4], const FragX3 (&A)[FT], FragX3 (&An)[FT],
-                                                   const uint4* __restrict__ wn, unsigned lo, BPair& B,
-                                                   const uint4* X16, int c, int cn, int g, int j, Side& side) {
+                                              int c, int cn, int g, int j, Side& side) {
   static_assert(FT == 4, "one next-chunk tile per sample group");
 #pragma unroll
   for (int sg = 0; sg < 4; ++sg) {
     if (sg == 0) side.load(X16, c);
     const BPair Bn = sg < 3 ? read_b(X16, c, sg + 1, g, j) : read_b(X16, cn, 0, g, j);
-    An[sg] = load_frag(wn + (lo + 2 * 64 * sg));
+    An[sg] = load_frag(wn + (lo + 2 * 64 * sg));   // wave-uniform base + 32-bit lane offset
 #pragma unroll
     for (int ft = 0; ft < FT; ++ft) {
       acc[ft][sg] = mfma32h(A[ft].hi, B.hi, ZERO ? floatx4{0.f, 0.f, 0.f, 0.f} : acc[ft][sg]);
@@ -290,12 +244,16 @@ __device__ __forceinline__ void chunk_step_sg_side(floatx4 (&acc)[FT][4], const 
   }
 }
 
-template <int FT, bool ZERO, typename Side>
-__device__ __forceinline__ void gemm_x3_sg_side(floatx4 (&acc)[FT][4], FragX3 (&A0)[FT], const uint4* __restrict__ W,
-                                                int KC, int cstride, const uint4* X16, int lane, Side side) {
+// A0 holds chunk 0's first NPF tiles (prefetch_a<FT, NPF>). No barrier in the
+// loop: the two waves of a SIMD drift apart by priority (field_x3_kernel).
+template <int FT, bool ZERO, int NPF = FT, typename Side = NoSide>
+__device__ __forceinline__ void gemm_x3_sg(floatx4 (&acc)[FT][4], FragX3 (&A0)[FT], const uint4* __restrict__ W,
+                                           int KC, int cstride, const uint4* X16, int lane, Side side = Side{}) {
   const int g = lane >> 4, j = lane & 15;
-  const unsigned lo = lane;
+  const unsigned lo = lane;          // W (wave-uniform) + lo: this lane's fragment
   FragX3 A1[FT];
+#pragma unroll
+  for (int ft = NPF; ft < FT; ++ft) A0[ft] = load_frag(W + (lo + 2 * 64 * ft));
   BPair B = read_b(X16, 0, 0, g, j);
   __builtin_amdgcn_sched_barrier(0);
   for (int c = 0; c < KC; c += 2) {
@@ -303,18 +261,30 @@ __device__ __forceinline__ void gemm_x3_sg_side(floatx4 (&acc)[FT][4], FragX3 (&
     const uint4* w1 = W + (int64_t)2 * (c + 1) * cstride;
     const uint4* w2 = W + (int64_t)2 * c2 * cstride;
     if (ZERO && c == 0)
-      chunk_step_sg_side<FT, true>(acc, A0, A1, w1, lo, B, X16, c, c + 1, g, j, side);
+      chunk_step_sg<FT, true>(acc, A0, A1, w1, lo, B, X16, c, c + 1, g, j, side);
     else
-      chunk_step_sg_side<FT, false>(acc, A0, A1, w1, lo, B, X16, c, c + 1, g, j, side);
-    chunk_step_sg_side<FT, false>(acc, A1, A0, w2, lo, B, X16, c + 1, c2, g, j, side);
+      chunk_step_sg<FT, false>(acc, A0, A1, w1, lo, B, X16, c, c + 1, g, j, side);
+    chunk_step_sg<FT, false>(acc, A1, A0, w2, lo, B, X16, c + 1, c2, g, j, side);
   }
+}
+
+// The K loop of one layer in a kernel's layout: 8 waves (TWO) run gemm_x3_sg on a fully prefetched chunk 0,
+// 4 waves gemm_x3 without its barrier. (The backward kernel, whose GEMMs carry a side task, calls the two
+// directly: passing the task through this selector changed field_bwd_x3_kernel<2, 4, *>'s code.)
+template <int FT, bool ZERO, bool TWO>
+__device__ __forceinline__ void gemm(floatx4 (&acc)[FT][4], FragX3 (&A0)[FT], const uint4* __restrict__ W, int KC,
+                                     int cstride, const uint4* X16, int lane) {
+  if constexpr (TWO)
+    gemm_x3_sg<FT, ZERO, FT>(acc, A0, W, KC, cstride, X16, lane);
+  else
+    gemm_x3<FT, ZERO, false>(acc, A0, W, KC, cstride, X16, lane);
 }
 
 // RowSide for 8 waves: waves w and w + 4 share sample 16 (w & 3) + j; wave w copies the K-chunks of parity w >> 2
 template <int HID>
 struct RowSide8 : RowSide {
   int par;
-  __device__ __forceinline__ void init8(float* rows0, float s_x, int64_t nrows, int w) {
+  __device__ __forceinline__ void start(float* rows0, float s_x, int64_t nrows, int w) {
     init<HID>(rows0, s_x, nrows, w & 3);
     par = w >> 2;
   }
@@ -350,7 +320,7 @@ __device__ __forceinline__ float act1(float x, float beta) {
 }
 
 template <int ACT>
-__device__ __forceinline__ floatx4 act4(floatx4 x, float beta) {
+__device__ __forceinline__ floatx4 act4(floatx4 x, float beta = 0.f) {
   if constexpr (ACT == 0) {
     x.x = fmaxf(x.x, 0.f); x.y = fmaxf(x.y, 0.f); x.z = fmaxf(x.z, 0.f); x.w = fmaxf(x.w, 0.f);
     return x;
@@ -502,8 +472,7 @@ __device__ __forceinline__ float prep_bn(floatx4 (&v)[FT][4], const floatx4 (&ac
     bn_tile<FT>(a4, c4, bn_a, bn_c, f, wid, ft, g);
 #pragma unroll
     for (int sg = 0; sg < 4; ++sg) {
-      floatx4 x = acc[ft][sg] * a4 + c4;
-      x.x = fmaxf(x.x, 0.f); x.y = fmaxf(x.y, 0.f); x.z = fmaxf(x.z, 0.f); x.w = fmaxf(x.w, 0.f);
+      const floatx4 x = act4<0>(acc[ft][sg] * a4 + c4);
       v[ft][sg] = x;
       mx = fmaxf(fmaxf(mx, x.x), fmaxf(fmaxf(x.y, x.z), x.w));
     }
@@ -555,8 +524,7 @@ __device__ __forceinline__ float publish_bn(uint4* X16, const floatx4 (&acc)[FT]
     const int ftg = FT * wid + ft;
 #pragma unroll
     for (int sg = 0; sg < 4; ++sg) {
-      floatx4 x = acc[ft][sg] * a4 + c4;
-      x.x = fmaxf(x.x, 0.f); x.y = fmaxf(x.y, 0.f); x.z = fmaxf(x.z, 0.f); x.w = fmaxf(x.w, 0.f);
+      const floatx4 x = act4<0>(acc[ft][sg] * a4 + c4);
       uint2 hi, lo;
       split4(x, s_x, hi, lo);
       const int s = 16 * sg + j;
@@ -577,6 +545,54 @@ __device__ __forceinline__ float publish_affine(uint4* X16, const floatx4 (&acc)
   lds_barrier();
   const float s_x = pow2_scale_for(red_max<NW>(red));
   store_split_affine<FT, BIAS, ACT>(X16, acc, f, bv, s_x, wid, g, j, beta);
+  lds_barrier();
+  return s_x;
+}
+
+// Training forward on the 8-wave layout (d_hidden 512: FT 4 x NW 8, two waves per SIMD as in inference; the
+// 4-wave layout's materialised layer input v does not fit its 256 registers): the two-pass publish of
+// act(acc * f [+ b]) also stores each value as its act row and its relu mask bit, the bits in the 4-wave
+// layout's mask words (mask_words8; field_bwd_x3_kernel<8, 4> reads them too); the workgroup's max goes to *lmax.
+template <int FT, int NW, bool BIAS>
+__device__ __forceinline__ float publish_affine_save(uint4* X16, const floatx4 (&acc)[FT][4], float f,
+                                                     const floatx4 (&bv)[FT], float mx, float* red, int wid, int lane,
+                                                     int g, int j, const FieldArgs& a, int layer, int64_t base,
+                                                     int64_t roff, float* lmax) {
+  static_assert(FT == 4 && NW == 8, "8-wave training forward: d_hidden 512");
+  constexpr int HID = 16 * FT * NW;
+  if (lane == 0) red[wid] = mx;
+  lds_barrier();
+  const float m = red_max<NW>(red);
+  if (wid == 0 && lane == 0) *lmax = m;
+  const float s_x = pow2_scale_for(m);
+  char* xb = reinterpret_cast<char*>(X16);
+  // the tile's rows from a wave-uniform base, 32-bit lane offsets recomputed here from an opaque lane id (hoisted
+  // out of the block loop, the per-row addresses would stay live across it and spill)
+  int ln = lane;
+  asm volatile("" : "+v"(ln));
+  g = ln >> 4;
+  j = ln & 15;
+  float* act = a.act + (int64_t)layer * a.act_stride + (roff + base) * HID;
+  const int nval = a.M - base < 64 ? (int)(a.M - base) : 64;
+  unsigned bits[2] = {0u, 0u};
+#pragma unroll
+  for (int ft = 0; ft < FT; ++ft) {
+    const int ftg = FT * wid + ft;
+#pragma unroll
+    for (int sg = 0; sg < 4; ++sg) {
+      const floatx4 y = relu_affine<BIAS, 0>(acc[ft][sg], f, bv[ft]);
+      uint2 hi, lo;
+      split4(y, s_x, hi, lo);
+      const int s = 16 * sg + j;
+      *reinterpret_cast<uint2*>(xb + xidx(ftg >> 1, 0, g, s) * 16 + (ftg & 1) * 8) = hi;
+      *reinterpret_cast<uint2*>(xb + xidx(ftg >> 1, 1, g, s) * 16 + (ftg & 1) * 8) = lo;
+      if (s < nval) __builtin_nontemporal_store(y, reinterpret_cast<floatx4*>(act + (unsigned)(s * HID + 16 * ftg + 4 * g)));
+      set_mask_bits(bits, y, ft, sg);
+    }
+  }
+  unsigned* mk = mask_words8(a.mask, layer, wid) + ln;
+  mk[0] = bits[0];
+  mk[64] = bits[1];
   lds_barrier();
   return s_x;
 }
