@@ -124,6 +124,9 @@ _SIGS = {
                      c_void_p, c_void_p, i64, c_int, c_void_p, c_void_p, c_void_p, c_void_p],
     "avr_raymarch_train": [ctypes.POINTER(ViewDesc), c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                            c_void_p, c_void_p, c_void_p, i64, c_int, c_void_p, c_void_p, c_void_p, c_void_p],
+    "avr_adaptive_front": [ctypes.POINTER(ViewDesc), c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                           c_void_p, c_void_p, c_void_p, c_void_p, u64, u64, c_void_p, i64, c_int, c_float, c_int,
+                           c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
     "avr_raymarch_bwd_scratch_bytes": [i64, c_int, i64, ctypes.POINTER(i64)],
     "avr_latent_tables_grad_points": [ctypes.POINTER(ViewDesc), c_int, c_void_p, i64, i64, c_int, c_int, c_void_p, i64,
                                       c_void_p, i64, c_void_p, c_void_p],

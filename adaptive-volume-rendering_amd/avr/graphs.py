@@ -1,7 +1,9 @@
 """HIP-graph replay of the inference renderer for fixed shapes (serving).
 
 `VolumeRenderer.forward` on the fused path is a fixed chain of launches (rays + stratified z, coarse field,
-composite, inverse-CDF sampling + merge, fine field, composite + depth) whose host side -- argument packing,
+composite, inverse-CDF sampling + merge, fine field, composite + depth), and so is a seeded
+`AdaptiveVolumeRenderer` / `Raymarcher` (rays, avr_adaptive_front, coarse-point field, depth, band field,
+composite, depth), whose host side -- argument packing,
 ctypes calls, tensor allocation -- costs tens of microseconds per launch. For small ray batches that host time
 is a large part of a frame. `GraphedRenderer` captures the chain once into a HIP graph (torch.cuda.CUDAGraph,
 hipGraph on ROCm) and replays it: new cameras / pixels are copied into the captured input buffers, the outputs
@@ -40,6 +42,9 @@ class GraphedRenderer:
     def __init__(self, renderer, net, cam2world, intrinsics, x_pix, warmup=2):
         if renderer.t_stop is not None:
             raise ValueError("GraphedRenderer: early termination sizes its launches on the host (t_stop must be None)")
+        if hasattr(renderer, "stage_host_draws") and renderer.seed is None:
+            raise ValueError("GraphedRenderer: the adaptive renderers draw their start distances on the host "
+                             "unless seeded (set renderer.seed)")
         self.renderer, self.net = renderer, net
         self.warmup = warmup
         self.c2w = cam2world.detach().clone().contiguous()
@@ -50,11 +55,16 @@ class GraphedRenderer:
 
     def _params(self):
         """The MLPs' parameters and buffers: updated in place (optimizer steps, load_state_dict), so their
-        versions are compared; the Parameter objects are collected once per capture."""
+        versions are compared; the Parameter objects are collected once per capture. The renderer's own
+        parameters too, when it has any (the adaptive renderers' LSTM and out_layer: the gate table made from
+        them is baked into the captured launches; VolumeRenderer has none)."""
         ts = []
         for mlp in (getattr(self.net, "mlp_coarse", None), getattr(self.net, "mlp_fine", None)):
             if mlp is not None:
                 ts += list(mlp.parameters()) + list(mlp.buffers())
+        renderer = getattr(self, "renderer", None)
+        if isinstance(renderer, torch.nn.Module):
+            ts += list(renderer.parameters())
         return ts
 
     def _views(self):
@@ -98,6 +108,8 @@ class GraphedRenderer:
         # eager call that replaces a cache entry (another scene count, another precision) cannot free them
         fused = getattr(net, "_fused", None)
         self._held_buffers = fused.cache_tensors() if fused is not None else []
+        if hasattr(renderer, "cache_tensors"):   # the adaptive renderers' gate tables
+            self._held_buffers = self._held_buffers + renderer.cache_tensors()
         self._held_precision = getattr(net, "field_precision", None)
         views = self._views()
         self._held_views = views

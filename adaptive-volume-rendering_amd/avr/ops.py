@@ -360,6 +360,40 @@ def raymarch(view, gate_table, lstm, out_layer, ro, rd, init_dist, steps, trace=
     return (world, fd, tr) if trace else (world, fd)
 
 
+def adaptive_front(views, gate_tables, lstm, out_layer, ro, rd, n_per_scene, steps, eps, n_band, init_dist=None,
+                   band_noise=None, seed=0, offset=0, ray_ids=None, want_draws=False, out=None):
+    """AdaptiveVolumeRenderer / Raymarcher inference front end in one launch (avr_adaptive_front): start distance,
+    LSTM march and the sorted band of len(views) scenes of n_per_scene rays. views: a ViewDesc array
+    (FusedField.views); gate_tables (n_scenes, H*W, 64); ro, rd (n, 3), n = n_scenes * n_per_scene.
+    init_dist (n) / band_noise (n, n_band): given draws, or None for in-kernel Philox keyed on offset + ray (or
+    offset + ray_ids[ray]). -> world (n, 3), z_sorted (n, n_band) or None (n_band = 0) [, init_out (n), noise_out
+    (n, n_band) or None: the draws used]. out: (world, z_sorted) to write into (slices of a larger call's)."""
+    n_scenes = len(views)
+    n = n_scenes * n_per_scene
+    ro, rd = _f32c(ro.reshape(n, 3)), _f32c(rd.reshape(n, 3))
+    ps = [_f32c(t.detach()) for t in (gate_tables, lstm.weight_hh, lstm.bias_ih, lstm.bias_hh,
+                                      out_layer.weight.reshape(-1), out_layer.bias.reshape(-1))]
+    if init_dist is not None:
+        init_dist = _f32c(init_dist.reshape(n))
+    if band_noise is not None:
+        band_noise = _f32c(band_noise.reshape(n, n_band))
+    ray_ids = _ray_ids(ray_ids, n)
+    require_device(ro, rd, init_dist, band_noise, *ps)
+    dev = ro.device
+    if out is None:
+        world = torch.empty(n, 3, device=dev, dtype=F32)
+        z = torch.empty(n, n_band, device=dev, dtype=F32) if n_band > 0 else None
+    else:
+        world, z = out
+        require_device(world, z)
+    init_out = torch.empty(n, device=dev, dtype=F32) if want_draws else None
+    noise_out = torch.empty(n, n_band, device=dev, dtype=F32) if want_draws and n_band > 0 else None
+    call("avr_adaptive_front", views, n_scenes, *[ptr(t) for t in ps], ptr(ro), ptr(rd), ptr(init_dist),
+         ptr(band_noise), int(seed), int(offset), ptr(ray_ids), int(n_per_scene), int(steps), float(eps), int(n_band),
+         ptr(world), ptr(z), ptr(init_out), ptr(noise_out), stream_of(ro))
+    return (world, z, init_out, noise_out) if want_draws else (world, z)
+
+
 def sum_of_products(pairs):
     """sum_i A_i @ B_i with the accumulation inside the GEMMs (addmm_, beta = 1): no separate add passes over the
     (rows, cols) partial products."""

@@ -3,6 +3,7 @@ harness, utils.py:481-537, on the fused path; BASELINE configs 4 and 5).
 
     python -m avr.render --frames 4 --res 800 [--t-stop 1e-5] [--out DIR]
     torchrun --nproc-per-node N -m avr.render ...   # rays of every frame sharded over N GPUs
+    python -m avr.render --renderer adaptive --n-coarse 20 --philox-seed 3   # in-kernel draws: reproducible frames
 
 Renders `--frames` views on the reference's camera ring (radius, height 0.4)
 of the synthetic scene (avr.scene) or of a NewPixelNeRFNet state_dict
@@ -37,6 +38,18 @@ def build_net(args, device):
     return net
 
 
+def adaptive_shard_fn(rend, net):
+    """The render_fn avr.parallel.render_sharded takes, for an AdaptiveVolumeRenderer: it passes the frame-wide
+    ray ids on (a seeded renderer's draws then match the single-GPU frame) and hands back the fine depth map
+    (SB, R) in both depth slots -- the renderer's third output is depth_coarse (SB, R, 1), which the packed
+    all_gather has no column for."""
+    def render_fn(cam2world, intrinsics, x_pix, ray_ids=None, n_rays_total=None):
+        rgb_c, rgb, _, depth_map = rend(cam2world, intrinsics, x_pix, net, ray_ids=ray_ids,
+                                        n_rays_total=n_rays_total)
+        return rgb_c, rgb, depth_map, depth_map
+    return render_fn
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--frames", type=int, default=4)
@@ -57,6 +70,9 @@ def main(argv=None):
                     help="VolumeRenderer (coarse/fine) or AdaptiveVolumeRenderer (LSTM march + band)")
     ap.add_argument("--raymarch-steps", type=int, default=10)
     ap.add_argument("--epsilon", type=float, default=0.05)
+    ap.add_argument("--philox-seed", type=int, default=None,
+                    help="adaptive renderer: in-kernel Philox draws with this seed (default: the reference's "
+                         "torch draws); a sharded frame then does not depend on the number of ranks")
     ap.add_argument("--out", default=None, help="directory for frame_XXX.ppm")
     args = ap.parse_args(argv)
 
@@ -86,6 +102,7 @@ def main(argv=None):
     if args.renderer == "adaptive":
         torch.manual_seed(args.seed + 2)
         rend = AdaptiveVolumeRenderer(net.d_latent, args.raymarch_steps, args.epsilon, args.n_coarse, True).to(device)
+        rend.seed = args.philox_seed
         samples_per_ray = args.n_coarse + 1 + args.raymarch_steps   # band + coarse point (+ LSTM lookups)
     else:
         rend = VolumeRenderer(args.near, args.far, args.n_coarse, args.n_fine, 0, 0.01, True)
@@ -106,7 +123,7 @@ def main(argv=None):
             if isinstance(rend, VolumeRenderer):   # Philox keyed by frame-wide ray ids
                 return render_sharded(lambda c, k, x, **ids: rend(c, k, x, net, **ids), c2w, K, x_pix,
                                       pass_ray_ids=True)
-            return render_sharded(lambda c, k, x: rend(c, k, x, net), c2w, K, x_pix)
+            return render_sharded(adaptive_shard_fn(rend, net), c2w, K, x_pix)
 
     for i in range(args.warmup):
         render(poses[i % len(poses)])

@@ -281,7 +281,13 @@ class _LSTMMarch(nn.Module):
         self.out_layer = nn.Linear(hidden_size, 1)
         self.counter = 0
         self._gate_cache = None
+        self._gates_cache = None   # the stacked per-scene tables of a multi-scene inference call
         self.last_path = None
+        # None: the reference's draws (CPU normal_, torch.rand); int: in-kernel Philox (inference on the fused path;
+        # training keeps the reference's draws)
+        self.seed = None
+        self._offset = 0
+        self.t_stop = None        # no early termination here (read by avr.graphs.GraphedRenderer)
         self._graph_init = None   # start distances read by a captured training step (stage_host_draws)
 
     def _initial_distance(self, SB, num_rays, device, noise):
@@ -348,9 +354,96 @@ class _LSTMMarch(nn.Module):
         self._gate_cache = (key, table, lat, w)
         return table
 
+    def _gate_tables(self, phi, SB):
+        """(SB, H*W, 64): scene s's table is _gate_table's product on latent[s] (the same call on the same
+        shapes, so a scene's table does not depend on the scenes it shares a call with); latent.shape[0] may be 1
+        (one table, repeated) or SB. Cached under _gate_table's key extended by the scene count."""
+        if SB == 1:
+            return self._gate_table(phi).unsqueeze(0)
+        lat = phi.encoder.latent
+        w = self.lstm.weight_ih
+        key = (param_generation(), lat.data_ptr(), lat._version, tuple(lat.shape), w.data_ptr(), w._version, SB)
+        if self._gates_cache is not None and self._gates_cache[0] == key:
+            return self._gates_cache[1]
+        C = lat.shape[1]
+        wt = w.detach().t().float()
+        one = [torch.matmul(lat[s].detach().reshape(C, -1).t().float(), wt) for s in range(lat.shape[0])]
+        tables = (torch.stack(one) if len(one) == SB else one[0].unsqueeze(0).repeat(SB, 1, 1)).contiguous()
+        self._gates_cache = (key, tables, lat, w)
+        return tables
+
+    def cache_tensors(self):
+        """The gate tables the inference launches read (avr.graphs.GraphedRenderer keeps them alive while a
+        captured graph reads them)."""
+        return [c[1] for c in (self._gate_cache, self._gates_cache) if c is not None]
+
+    def _net_fusable(self, phi, ros):
+        return (not torch.is_grad_enabled() and hasattr(phi, "can_fuse") and phi.can_fuse(ros)
+                and phi.encoder.latent.shape[1] == self.n_feature_channels)
+
     def can_fuse(self, phi, ros):
-        return (ros.shape[0] == 1 and not torch.is_grad_enabled() and hasattr(phi, "can_fuse")
-                and phi.can_fuse(ros) and phi.encoder.latent.shape[1] == self.n_feature_channels)
+        return ros.shape[0] == 1 and self._net_fusable(phi, ros)
+
+    def _front_path(self, phi, xy_pix, n_band=0):
+        """Inference through avr_adaptive_front (one launch for the start distance, the march and the band): several
+        scenes, a Philox seed, or a HIP-graph capture (which cannot take the host draw). One scene with the
+        reference's draws outside a capture keeps the kernel chain it always had, bit for bit."""
+        SB = xy_pix.shape[0]
+        if not (xy_pix.is_cuda and self._net_fusable(phi, xy_pix)):
+            return False
+        ok = (phi.encoder.latent.shape[0] in (1, SB) and self.lstm.bias and self.lstm.hidden_size == 16
+              and n_band <= 64)
+        if self.seed is not None and not ok:
+            # the Philox draws exist in that kernel only: no quiet change to other draws
+            raise ValueError("seeded adaptive inference needs n_coarse <= 64, an LSTMCell(hidden 16, bias) and one "
+                             "latent map per scene (or one for all)")
+        return ok and (SB > 1 or self.seed is not None or torch.cuda.is_current_stream_capturing())
+
+    def _infer_front(self, cam2world, intrinsics, xy_pix, phi, noise, ray_ids, n_rays_total, n_band, eps=0.0):
+        """-> ros, rds, c2w_info, world (SB, R, 3), z_sorted (SB * R, n_band) or None, rgb and depth (SB, R, 1) of
+        the coarse field at the marched points. No torch arithmetic, sort or host-to-device copy; no host read of
+        device memory once the gate tables and view descriptors are cached."""
+        SB, R, _ = xy_pix.shape
+        dev = xy_pix.device
+        self.last_path = "fused"
+        ros, rds, c2w_info = ops.world_rays(xy_pix, intrinsics, cam2world)
+        seeded = self.seed is not None
+        seed, off = (self.seed or 0), self._offset
+        ids = None
+        if ray_ids is not None and seeded:
+            ids = ray_ids.to(dev, torch.int64).reshape(-1)   # scene 0's ids as they are: no kernel for one scene
+            if SB > 1:
+                ids = (torch.arange(SB, device=dev, dtype=torch.int64)[:, None] * int(n_rays_total)
+                       + ids.reshape(1, R)).reshape(-1)
+        if seeded:
+            self._offset += SB * (R if ray_ids is None else int(n_rays_total))
+        # an explicit noise dict overrides the draws it names; otherwise Philox (seeded) or the reference's draws
+        init = band = None
+        if noise is not None and "initial_distance" in noise or not seeded:
+            init = self._initial_distance(SB, R, dev, noise).reshape(SB * R)
+        if n_band > 0:
+            band = None if noise is None else noise.get("band")
+            if band is None and not seeded:
+                band = _noise((SB, R, n_band), xy_pix, "rand")   # sample_coarse's draw
+            if band is not None:
+                band = band.reshape(SB * R, n_band)
+        fused = phi.fused()
+        tables = self._gate_tables(phi, SB)
+        world = torch.empty(SB * R, 3, device=dev, dtype=torch.float32)
+        z = torch.empty(SB * R, n_band, device=dev, dtype=torch.float32) if n_band > 0 else None
+        ro_f, rd_f = ros.reshape(SB * R, 3), rds.reshape(SB * R, 3)
+        for g0, n in _lib.scene_groups(SB):
+            a, b = g0 * R, (g0 + n) * R
+            ops.adaptive_front(fused.views(range(g0, g0 + n)), tables[g0:g0 + n], self.lstm, self.out_layer,
+                               ro_f[a:b], rd_f[a:b], R, self.steps, eps, n_band,
+                               init_dist=None if init is None else init[a:b],
+                               band_noise=None if band is None else band[a:b], seed=seed,
+                               offset=off if ids is not None else off + a, ray_ids=None if ids is None else ids[a:b],
+                               out=(world[a:b], None if z is None else z[a:b]))
+        world = world.reshape(SB, R, 3)
+        coarse = fused.forward_points(world, rds, True)
+        depth_coarse = ops.depth_of_points(world, c2w_info).reshape(SB, R, -1)
+        return ros, rds, c2w_info, world, z, coarse[..., :3].reshape(SB, R, 3), depth_coarse
 
     def can_train_fused(self, phi, ros, rds, init_dist):
         """Autograd through the march on HIP (avr_raymarch_train / _bwd): the net's latent lookup is the fused
@@ -520,8 +613,15 @@ class Raymarcher(_LSTMMarch):
     def __init__(self, num_feature_channels, raymarch_steps):
         super().__init__(num_feature_channels, raymarch_steps)
 
-    def forward(self, cam2world, intrinsics, xy_pix, phi, noise=None):
+    def forward(self, cam2world, intrinsics, xy_pix, phi, noise=None, ray_ids=None, n_rays_total=None):
+        """ray_ids (R,) / n_rays_total: as VolumeRenderer.forward (the seeded start distances are keyed by the
+        frame-wide ray index)."""
         SB, num_rays, _ = xy_pix.shape
+        if self._front_path(phi, xy_pix):
+            _, _, _, _, _, rgb, final_depth = self._infer_front(cam2world, intrinsics, xy_pix, phi, noise, ray_ids,
+                                                                n_rays_total, 0)
+            self.counter += 1
+            return rgb, None, final_depth, final_depth
         ros, rds, c2w_info = ops.world_rays(xy_pix, intrinsics, cam2world)
         init = self._initial_distance(SB, num_rays, xy_pix.device, noise)
         world = self.march(ros, rds, init, phi)
@@ -548,9 +648,22 @@ class AdaptiveVolumeRenderer(_LSTMMarch):
         self.n_coarse = n_coarse
         self.white_back = white_back
 
-    def forward(self, cam2world, intrinsics, xy_pix, phi, debug=False, noise=None):
+    def forward(self, cam2world, intrinsics, xy_pix, phi, debug=False, noise=None, ray_ids=None, n_rays_total=None):
+        """ray_ids (R,) / n_rays_total: as VolumeRenderer.forward (the seeded draws are keyed by the frame-wide
+        ray index, so a sharded render equals the single-GPU render of the same seed)."""
         SB, num_rays, _ = xy_pix.shape
         dev = xy_pix.device
+        if self._front_path(phi, xy_pix, self.n_coarse):
+            n = self.n_coarse
+            ros, rds, c2w_info, _, z_sorted, rgb_coarse, depth_coarse = self._infer_front(
+                cam2world, intrinsics, xy_pix, phi, noise, ray_ids, n_rays_total, n, self.epsilon)
+            fused = phi.fused()
+            field = (fused.forward_rays(ros[0], rds[0], z_sorted, False) if SB == 1
+                     else fused.forward_rays_batch(ros, rds, z_sorted, False)).reshape(SB, num_rays, n, 4)
+            rgb, distance_map, _ = volume_integral_packed(z_sorted.reshape(SB, num_rays, n), field,
+                                                          white_back=self.white_back)
+            depth_map = ops.depth_from_world(ros, rds, distance_map.reshape(SB, num_rays), c2w_info)
+            return rgb_coarse, rgb, depth_coarse, depth_map
         ros, rds, c2w_info = ops.world_rays(xy_pix, intrinsics, cam2world)
         init = self._initial_distance(SB, num_rays, dev, noise)
         world = self.march(ros, rds, init, phi)

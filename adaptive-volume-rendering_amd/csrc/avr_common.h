@@ -115,6 +115,12 @@ __device__ __forceinline__ float mask_select(uint64_t m, float clear, float set)
 
 // ------------------------------------------------------------------ Philox4x32-10
 // Counter-based RNG for in-kernel noise (no noise bytes read from HBM).
+// Streams (counter word 3; include/avr.h): coarse noise; the fine pass's (u, u2) pair (one block per fine
+// sample: u = .x, u2 = .y); the depth samples' normals (sampling.hip); the LSTM march's start distance (block 0)
+// and the adaptive band's noise (sample i = word i & 3 of block i >> 2) (adaptive.hip).
+constexpr uint32_t kStreamCoarse = 0x1001u, kStreamFine = 0x2002u, kStreamDepth = 0x4004u;
+constexpr uint32_t kStreamMarch = 0x8008u, kStreamBand = 0x10010u;
+
 __device__ __forceinline__ uint4 philox4x32(uint4 c, uint2 k) {
 #pragma unroll
   for (int i = 0; i < 10; ++i) {

@@ -14,14 +14,9 @@
 // of gathers per ray and step instead of 4 x 2 KB plus a 512 x 64 GEMV.
 // One ray per 16 lanes; lane k owns hidden unit k (its 4 gate rows of W_hh
 // stay in registers, h_j comes in by 16-lane shuffles).
-#include "field_common.h"
+#include "lstm_march.h"
 
 namespace avr {
-
-constexpr int kHid = 16;           // LSTMCell hidden size (renderers.py:301, :370)
-constexpr int kGates = 4 * kHid;   // i, f, g, o
-
-__device__ __forceinline__ float sigmoid_(float x) { return fdiv(1.0f, fadd(1.0f, expf(-x))); }
 
 __global__ void __launch_bounds__(256) raymarch_kernel(View v, const float* __restrict__ table,
                                                        const float* __restrict__ w_hh, const float* __restrict__ b_ih,
@@ -34,14 +29,7 @@ __global__ void __launch_bounds__(256) raymarch_kernel(View v, const float* __re
   const int64_t ray_raw = (int64_t)blockIdx.x * (blockDim.x / kHid) + threadIdx.x / kHid;
   const bool live = ray_raw < n_rays;
   const int64_t ray = live ? ray_raw : n_rays - 1;   // keep the 16-lane group whole for the shuffles
-  float wr[4][kHid], bias[4];
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {
-#pragma unroll
-    for (int j = 0; j < kHid; ++j) wr[q][j] = w_hh[(q * kHid + k) * kHid + j];
-    bias[q] = fadd(b_ih[q * kHid + k], b_hh[q * kHid + k]);
-  }
-  const float wo = w_out[k], bo = b_out[0];
+  const MarchLane L = march_lane(w_hh, b_ih, b_hh, w_out, b_out, k);
   const float r0 = ro[3 * ray], r1 = ro[3 * ray + 1], r2 = ro[3 * ray + 2];
   const float e0 = rd[3 * ray], e1 = rd[3 * ray + 1], e2 = rd[3 * ray + 2];
   const float dist0 = d0[ray];
@@ -49,31 +37,8 @@ __global__ void __launch_bounds__(256) raymarch_kernel(View v, const float* __re
   if (trace && live && k < 3) trace[3 * ray + k] = k == 0 ? x0 : (k == 1 ? x1 : x2);
   float h = 0.f, c = 0.f;
   for (int s = 0; s < steps; ++s) {
-    const Bilinear bl = bilinear_at(v, x0, x1, x2);
-    float g[4];
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      // W_ih v + b_ih: bilinear blend of the per-texel projections
-      const int row = q * kHid + k;
-      const float p = ((table[(int64_t)bl.tex[0] * kGates + row] * bl.w[0] +
-                        table[(int64_t)bl.tex[1] * kGates + row] * bl.w[1]) +
-                       table[(int64_t)bl.tex[2] * kGates + row] * bl.w[2]) +
-                      table[(int64_t)bl.tex[3] * kGates + row] * bl.w[3];
-      g[q] = p + bias[q];
-    }
-#pragma unroll
-    for (int j = 0; j < kHid; ++j) {
-      const float hj = __shfl(h, j, kHid);
-#pragma unroll
-      for (int q = 0; q < 4; ++q) g[q] = fmaf(wr[q][j], hj, g[q]);
-    }
-    const float ig = sigmoid_(g[0]), fg = sigmoid_(g[1]), gg = tanhf(g[2]), og = sigmoid_(g[3]);
-    c = fadd(fmul(fg, c), fmul(ig, gg));
-    h = fmul(og, tanhf(c));
-    float sd = fmul(wo, h);
-#pragma unroll
-    for (int d = kHid / 2; d > 0; d >>= 1) sd = fadd(sd, __shfl_xor(sd, d, kHid));
-    sd = fadd(sd, bo);
+    MarchGateValues gates;
+    const float sd = march_step(v, table, L, x0, x1, x2, h, c, gates);
     x0 = fadd(x0, fmul(e0, sd));   // world_coords + rds * signed_distance (renderers.py:341, :432)
     x1 = fadd(x1, fmul(e1, sd));
     x2 = fadd(x2, fmul(e2, sd));
@@ -97,9 +62,6 @@ __global__ void __launch_bounds__(256) raymarch_kernel(View v, const float* __re
 //   dx += R^T d(xc) of the bilinear lookup's position gradient (grid_sample border / align_corners=True
 //         backward: zero where the coordinate was clipped)
 // with W_hh, the biases and out_layer's gradients summed per workgroup.
-struct MarchScenes {
-  View v[AVR_MAX_SCENES];
-};
 constexpr int kMarchState = 6 * kHid;   // per ray and step: h, c, i, f, g, o
 
 // Lookup geometry of a point with the derivatives of the continuous texel coordinates (ix, iy) with respect
@@ -160,14 +122,7 @@ __global__ void __launch_bounds__(256) raymarch_train_kernel(MarchScenes sc, con
   const int scene = (int)(ray / n_per_scene);
   const View& v = sc.v[scene];
   const float* table = tables + scene * table_stride;
-  float wr[4][kHid], bias[4];
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {
-#pragma unroll
-    for (int j = 0; j < kHid; ++j) wr[q][j] = w_hh[(q * kHid + k) * kHid + j];
-    bias[q] = fadd(b_ih[q * kHid + k], b_hh[q * kHid + k]);
-  }
-  const float wo = w_out[k], bo = b_out[0];
+  const MarchLane L = march_lane(w_hh, b_ih, b_hh, w_out, b_out, k);
   const float e0 = rd[3 * ray], e1 = rd[3 * ray + 1], e2 = rd[3 * ray + 2];
   const float dist0 = d0[ray];
   float x0 = fadd(ro[3 * ray], fmul(e0, dist0)), x1 = fadd(ro[3 * ray + 1], fmul(e1, dist0));
@@ -175,35 +130,13 @@ __global__ void __launch_bounds__(256) raymarch_train_kernel(MarchScenes sc, con
   if (live && k < 3) trace[3 * ray + k] = k == 0 ? x0 : (k == 1 ? x1 : x2);
   float h = 0.f, c = 0.f;
   for (int s = 0; s < steps; ++s) {
-    const Bilinear bl = bilinear_at(v, x0, x1, x2);
-    float g[4];
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const int row = q * kHid + k;
-      const float p = ((table[(int64_t)bl.tex[0] * kGates + row] * bl.w[0] +
-                        table[(int64_t)bl.tex[1] * kGates + row] * bl.w[1]) +
-                       table[(int64_t)bl.tex[2] * kGates + row] * bl.w[2]) +
-                      table[(int64_t)bl.tex[3] * kGates + row] * bl.w[3];
-      g[q] = p + bias[q];
-    }
-#pragma unroll
-    for (int j = 0; j < kHid; ++j) {
-      const float hj = __shfl(h, j, kHid);
-#pragma unroll
-      for (int q = 0; q < 4; ++q) g[q] = fmaf(wr[q][j], hj, g[q]);
-    }
-    const float ig = sigmoid_(g[0]), fg = sigmoid_(g[1]), gg = tanhf(g[2]), og = sigmoid_(g[3]);
-    c = fadd(fmul(fg, c), fmul(ig, gg));
-    h = fmul(og, tanhf(c));
+    MarchGateValues gates;
+    const float sd = march_step(v, table, L, x0, x1, x2, h, c, gates);
     if (live) {
       float* st = state + ((int64_t)s * n_rays + ray) * kMarchState;
       st[k] = h; st[kHid + k] = c;
-      st[2 * kHid + k] = ig; st[3 * kHid + k] = fg; st[4 * kHid + k] = gg; st[5 * kHid + k] = og;
+      st[2 * kHid + k] = gates.ig; st[3 * kHid + k] = gates.fg; st[4 * kHid + k] = gates.gg; st[5 * kHid + k] = gates.og;
     }
-    float sd = fmul(wo, h);
-#pragma unroll
-    for (int d = kHid / 2; d > 0; d >>= 1) sd = fadd(sd, __shfl_xor(sd, d, kHid));
-    sd = fadd(sd, bo);
     x0 = fadd(x0, fmul(e0, sd));
     x1 = fadd(x1, fmul(e1, sd));
     x2 = fadd(x2, fmul(e2, sd));
@@ -475,17 +408,6 @@ __global__ void __launch_bounds__(256) raymarch_table_finish_kernel(const unsign
 }  // namespace avr
 
 using namespace avr;
-
-static int march_scenes(const avr_view_desc* views, int n_scenes, MarchScenes* sc, const char* what) {
-  AVR_REQUIRE(views && n_scenes >= 1 && n_scenes <= AVR_MAX_SCENES, "%s: 1..%d scenes", what, AVR_MAX_SCENES);
-  for (int s = 0; s < n_scenes; ++s) {
-    AVR_REQUIRE(views[s].latent_h == views[0].latent_h && views[s].latent_w == views[0].latent_w &&
-                    views[s].latent_h > 0 && views[s].latent_w > 0,
-                "%s: scenes need latent maps of one (positive) size", what);
-    view_from_desc(&views[s], &sc->v[s]);
-  }
-  return AVR_OK;
-}
 
 extern "C" int avr_raymarch_train(const avr_view_desc* views, int n_scenes, const float* gate_tables,
                                   const float* w_hh, const float* b_ih, const float* b_hh, const float* w_out,

@@ -561,6 +561,31 @@ int avr_raymarch_bwd(const avr_view_desc* views, int n_scenes, const float* gate
                      const float* grad_world, int64_t n_per_scene, int steps, int lookup_grad, float* d_tables,
                      float* d_grads, void* scratch, int64_t scratch_bytes, void* stream);
 
+/* AdaptiveVolumeRenderer / Raymarcher inference front end (renderers.py:313-343, :380-432, :490-496), n_scenes
+ * (<= AVR_MAX_SCENES) scenes of n_per_scene rays (ray r in scene r / n_per_scene: its view and gate table), in
+ * one launch. Added within ABI 18 (no version change). Per ray:
+ *   start distance  init_dist[r], or with init_dist NULL 0.8 + 0.05 * N(0, 1) (the reference's
+ *                   normal_(mean=0.8, std=5e-2)) from Philox;
+ *   world (n, 3)    the march of avr_raymarch from ro + rd * start (the same instructions: for one scene and a
+ *                   given init_dist, bit-equal to avr_raymarch's world);
+ *   z_sorted (n, n_band), n_band > 0: d = (world_x - ro_x) / rd_x (quirk kept; rd_x = 0 gives a NaN row),
+ *                   z_i = ((d - eps) + span * (i / n_band)) + (u_i * span) / n_band, span = (d + eps) - (d - eps),
+ *                   sorted ascending: avr_band_fwd's z bit for bit for the same world and noise. u = band_noise
+ *                   (n, n_band), or with band_noise NULL Philox uniforms. n_band = 0 (Raymarcher): no band,
+ *                   z_sorted may be NULL.
+ * Philox draws use key = offset + (ray_ids ? ray_ids[r] : r), as avr_sample_coarse keys its draws. Streams
+ * (counter word 3) of the library: 0x1001 coarse noise, 0x2002 fine (u, u2), 0x4004 depth normals
+ * (avr_sample_coarse / avr_sample_fine); 0x8008 the march's start distance (Box-Muller on words 0, 1 of block
+ * 0); 0x10010 the band noise (sample i = word i & 3 of block i >> 2).
+ * init_out (n) / noise_out (n, n_band), when not NULL, receive the start distances / band noise used (drawn or
+ * given). n_per_scene = 0 returns AVR_OK without a launch. */
+int avr_adaptive_front(const avr_view_desc* views, int n_scenes, const float* gate_tables, const float* w_hh,
+                       const float* b_ih, const float* b_hh, const float* w_out, const float* b_out,
+                       const float* ro, const float* rd, const float* init_dist, const float* band_noise,
+                       uint64_t seed, uint64_t offset, const int64_t* ray_ids, int64_t n_per_scene, int steps,
+                       float eps, int n_band, float* world, float* z_sorted, float* init_out, float* noise_out,
+                       void* stream);
+
 /* ------------------------------------------------- training loss and metrics
  * ABI 17: loss_fn (utils.py:364-377) over n_rays rays without a host sync, so it can be recorded in a HIP-graph
  * capture. terms = AVR_LOSS_COARSE | AVR_LOSS_FINE | AVR_LOSS_DEPTH selects
