@@ -18,6 +18,7 @@ AVR_LOOKUP_GRAD_TERMS = 8
 ABI_VERSION = 18
 ADAM_CHUNK = 4096          # avr.h AVR_ADAM_CHUNK: elements per work chunk of avr_adam_step
 ADAM_MAX_TENSORS = 88      # avr.h AVR_ADAM_MAX_TENSORS: tensors per avr_adam_step launch
+LATENT_ADJOINT_CHUNK = 512  # avr.h AVR_LATENT_ADJOINT_CHUNK: rows per gather wave of avr_latent_features_adjoint
 
 
 def scene_groups(n):
@@ -173,6 +174,9 @@ _SIGS = {
     "avr_latent_features_batch": [ctypes.POINTER(ViewDesc), c_int, c_void_p, c_int, c_void_p, i64, c_void_p, c_void_p],
     "avr_latent_features_grad_points": [ctypes.POINTER(ViewDesc), c_int, c_void_p, c_int, c_void_p, i64, c_void_p,
                                         c_void_p, c_void_p],
+    "avr_latent_features_adjoint_scratch_bytes": [c_int, i64, c_int, c_int, c_int, ctypes.POINTER(i64)],
+    "avr_latent_features_adjoint": [ctypes.POINTER(ViewDesc), c_int, c_void_p, i64, c_void_p, i64, c_int, c_void_p,
+                                    c_void_p, i64, c_void_p],
     "avr_bn_layer_run": [ctypes.POINTER(FieldDims), ctypes.POINTER(BnLayer), c_void_p],
     "avr_bn_partial_floats": [i64, c_int, ctypes.POINTER(i64)],
     "avr_bn_stats": [c_void_p, i64, c_int, c_void_p, c_float, c_float, c_void_p, c_void_p, c_void_p, c_void_p,

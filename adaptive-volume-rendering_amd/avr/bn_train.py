@@ -24,7 +24,7 @@ import torch
 from . import _lib, ops
 from ._lib import BnLayer, call, ptr, stream_of
 from .field import fused_eligible, softplus_beta, train_param_names, uses_bn
-from .train_common import (forward_train, input_grads_via_autograd, lin_z_epilogue, lookup_features,
+from .train_common import (forward_train, input_grads, lin_z_epilogue, lookup_features,
                            padded_z_features)
 
 F32 = torch.float32
@@ -295,6 +295,6 @@ class _FieldTrainBN(torch.autograd.Function):
             g_feat = ops.sum_of_products([(Gx[b], P[f"lin_z.{b}.weight"].detach()) for b in range(nz)])
         if want_xyz:
             g_zf = Gx[0] @ P["lin_in.weight"].detach()
-        d_latent, d_xyz = input_grads_via_autograd(net, xyz, viewdirs, latent, want_latent, want_xyz, g_feat, g_zf)
+        d_latent, d_xyz = input_grads(fused, xyz, viewdirs, latent, want_latent, want_xyz, g_feat, g_zf)
         return (None, None, None, d_xyz, None, d_latent) + tuple(
             grads[n] if ctx.needs_input_grad[6 + i] else None for i, n in enumerate(names))

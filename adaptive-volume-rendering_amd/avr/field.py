@@ -25,7 +25,7 @@ from torch.optim.optimizer import register_optimizer_step_post_hook
 
 from . import _lib, ops, train_common
 from ._lib import FieldDims, ResnetFCWeights, ViewDesc, call, ptr, require_device, scene_groups, stream_of
-from .train_common import input_grads_via_autograd, lookup_features
+from .train_common import input_grads, latent_grad_hip, latent_grad_on_hip, lookup_features
 
 F32 = torch.float32
 
@@ -272,6 +272,9 @@ class FusedField:
             raise ValueError(f"precision must be one of {sorted(PRECISIONS)}")
         self.precision = precision
         self.net = net
+        # how the last training backward formed d loss / d latent: "hip" (avr_latent_features_adjoint) | "autograd"
+        # (torch's grid_sample adjoint), None before the first (for tests / introspection, as renderers' last_path)
+        self.last_latent_grad = None
         # the caches: slot -> _Record, read and filled by _cached (packed() alone keeps its own body)
         self._packed = {}         # coarse, or (coarse, "bn_train") -> _Record of a _Packed (tables hang off it)
         self._view_cache = {}     # (sb, ns) -> ViewDesc (view())
@@ -792,10 +795,11 @@ class _FieldTrain(torch.autograd.Function):
     weight and bias gradient in one batched split-K x3 GEMM over all samples
     (_weight_grads: fc_0 / fc_1 against the saved inputs, lin_z against the
     interpolated latent (grid_sample, models.py:266-273), lin_in against the
-    positional-encoded input). The points get their gradient on HIP when they alone
-    want one (_point_grad_hip); otherwise the inputs' gradients go through torch's
-    input functions (input_grads_via_autograd): the latent map gets the grid_sample
-    adjoint of sum_b G_z[b] W_z[b] when it requires grad."""
+    positional-encoded input). The latent maps get the lookup's adjoint of
+    sum_b G_z[b] W_z[b] on HIP when they require grad (latent_grad_hip:
+    deterministic, no float atomics), the points their gradient on HIP as well
+    (_point_grad_hip); what neither covers goes through torch's input functions
+    (input_grads: one map shared by several scenes, AVR_LATENT_GRAD_VIA_AUTOGRAD=1)."""
 
     @staticmethod
     def forward(ctx, fused, coarse, names, xyz, viewdirs, latent, *params):
@@ -864,11 +868,17 @@ class _FieldTrain(torch.autograd.Function):
         d4, d4_max = ops.lin_out_act_bwd(grad_out, out)
         grads = _weight_grads(dims, Mt, G, g_max, act, act_max, lat_feat, lat_max, zf, d4, d4_max)
         d_latent = d_xyz = None
-        if want_xyz and not want_latent and (net.stop_encoder_grad or (nz > 0 and SB <= latent.shape[0])):
+        points_on_hip = want_xyz and (net.stop_encoder_grad or (nz > 0 and SB <= latent.shape[0]))
+        if points_on_hip and want_latent and latent_grad_on_hip(latent, SB):
+            # both on HIP: the maps' gradient from the lookup's adjoint, the points' as when they alone want one
+            fused.last_latent_grad = "hip"
+            d_latent = latent_grad_hip(fused, latent, xyz, _feat_grad(fused, entry, bwd, Gz, P, Mt))
+            d_xyz = _point_grad_hip(fused, entry, bwd, ctx.tables, xyz, viewdirs, latent, p, G[2 * nb], Gz, P)
+        elif points_on_hip and not want_latent:
             d_xyz = _point_grad_hip(fused, entry, bwd, ctx.tables, xyz, viewdirs, latent, p, G[2 * nb], Gz, P)
         elif want_latent or want_xyz:
             g_feat = _feat_grad(fused, entry, bwd, Gz, P, Mt) if nz > 0 else None
             g_zf = G[2 * nb] @ P["lin_in.weight"].detach() if want_xyz else None
-            d_latent, d_xyz = input_grads_via_autograd(net, xyz, viewdirs, latent, want_latent, want_xyz, g_feat, g_zf)
+            d_latent, d_xyz = input_grads(fused, xyz, viewdirs, latent, want_latent, want_xyz, g_feat, g_zf)
         return (None, None, None, d_xyz, None, d_latent) + tuple(
             grads[n] if ctx.needs_input_grad[6 + i] else None for i, n in enumerate(names))

@@ -27,7 +27,7 @@ from . import _lib, ops
 from ._lib import stream_of
 from .field import _feat_grad, fused_eligible, softplus_beta, train_param_names, uses_bn
 from .models import combine_interleaved
-from .train_common import (forward_train, gather_rows as _gather, input_grads_via_autograd, lin_z_epilogue,
+from .train_common import (forward_train, gather_rows as _gather, input_grads, lin_z_epilogue,
                            padded_z_features)
 
 F32 = torch.float32
@@ -271,6 +271,6 @@ class _FieldTrainLayers(torch.autograd.Function):
                 g_feat = _feat_grad(fused, entry, bwd, Gz, P, M1)
         if want_xyz:
             g_zf = g_in0 @ P["lin_in.weight"].detach()
-        d_latent, d_xyz = input_grads_via_autograd(net, xyz, viewdirs, latent, want_latent, want_xyz, g_feat, g_zf)
+        d_latent, d_xyz = input_grads(fused, xyz, viewdirs, latent, want_latent, want_xyz, g_feat, g_zf, NS)
         return (None, None, None, d_xyz, None, d_latent) + tuple(
             grads[n] if ctx.needs_input_grad[6 + i] else None for i, n in enumerate(names))

@@ -587,6 +587,38 @@ def latent_features(view, latent_chw, xyz, out=None, hwc=None):
     return out
 
 
+def latent_features_adjoint(views, xyz, grad_features, hw):
+    """The lookup's adjoint onto the maps (avr_latent_features_adjoint: grid_sample's input gradient, bilinear /
+    border / align_corners=True, deterministic: no float atomics): views a ViewDesc array of n_scenes source views
+    (avr.field.FusedField.views) with maps of hw = (H, W), xyz (n_scenes, n_points, 3), grad_features
+    (n_scenes * n_points, C) rows of unit channel stride -> (n_scenes, H*W, C) channels-last, every row written.
+    One call per _lib.AVR_MAX_SCENES scenes; the scratch comes from torch's allocator (no host read: capturable)."""
+    H, W = hw
+    n_scenes, n_points = xyz.shape[0], xyz.shape[1]
+    C = grad_features.shape[1]
+    xyz = _f32c(xyz)
+    if (grad_features.dtype != F32 or grad_features.stride(1) != 1 or grad_features.stride(0) % 4
+            or grad_features.data_ptr() % 16):
+        grad_features = grad_features.to(F32).contiguous()
+    if grad_features.shape[0] != n_scenes * n_points or len(views) != n_scenes:
+        raise _lib.AVRError("latent_features_adjoint: %d gradient rows and %d views for %d x %d points"
+                            % (grad_features.shape[0], len(views), n_scenes, n_points))
+    require_device(xyz)
+    ld = grad_features.stride(0) if grad_features.shape[0] > 1 else C
+    out = torch.empty(n_scenes, H * W, C, device=xyz.device, dtype=F32)
+    lib = _lib.load()
+    for g0, n in _lib.scene_groups(n_scenes):
+        vs = views if n == n_scenes else (_lib.ViewDesc * n)(*views[g0:g0 + n])
+        nb = ctypes.c_int64(0)
+        _lib.check(lib.avr_latent_features_adjoint_scratch_bytes(n, n_points, H, W, C, ctypes.byref(nb)),
+                   "avr_latent_features_adjoint_scratch_bytes")
+        scratch = torch.empty(max(nb.value, 16), device=xyz.device, dtype=torch.uint8)
+        call("avr_latent_features_adjoint", vs, n, ptr(xyz[g0]), n_points,
+             ctypes.c_void_p(grad_features.data_ptr() + g0 * n_points * ld * 4), ld, C, ptr(out[g0]), ptr(scratch),
+             nb.value, stream_of(xyz))
+    return out
+
+
 def adam_step(tensors, lr, beta1, beta2, eps, weight_decay, step):
     """One Adam step (train.py:112-114, :299) of `tensors`, a list of (param, grad, exp_avg, exp_avg_sq) fp32
     device tensors whose four members share one dense element order, in place; `step` is the 0-dim fp32 device

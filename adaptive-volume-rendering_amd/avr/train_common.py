@@ -1,8 +1,10 @@
 """What the three training Functions share (avr.field._FieldTrain, avr.bn_train._FieldTrainBN,
 avr.layer_train._FieldTrainLayers): the rf(xyz, viewdirs, coarse) entry, the layer paths' padded z_feature
-operand and lin_z epilogue, the interpolated-latent lookup and the input gradients through torch autograd of
-net.mlp_inputs. Nothing here imports avr.field: a FusedField comes in as an argument."""
+operand and lin_z epilogue, the interpolated-latent lookup and the input gradients: the latent maps' through the
+lookup's HIP adjoint (avr_latent_features_adjoint), the rest through torch autograd of net.mlp_inputs. Nothing here
+imports avr.field: a FusedField comes in as an argument."""
 import ctypes
+import os
 
 import torch
 
@@ -64,6 +66,44 @@ def lookup_features(fused, latent, p, n_scenes, B, ns=1):
         ops.latent_features(fused.view(sb, ns), latent[s], p[sb], out=out[sb * B:(sb + 1) * B],
                             hwc=fused.latent_hwc(latent, s))
     return out
+
+
+def latent_grad_on_hip(latent, n_maps):
+    """Whether d loss / d latent comes from the lookup's HIP adjoint (latent_grad_hip): an fp32 device map per
+    (scene, view) -- one map shared by several scenes keeps the autograd path, which sums over them --, and not
+    AVR_LATENT_GRAD_VIA_AUTOGRAD=1 (the earlier path, kept in the build for A/B). The callers' nets are
+    fused_eligible (or its bn / layer equivalent): bilinear lookup, border padding."""
+    return (latent.dtype == F32 and latent.is_cuda and latent.dim() == 4 and latent.shape[0] == n_maps
+            and os.environ.get("AVR_LATENT_GRAD_VIA_AUTOGRAD") != "1")
+
+
+def latent_grad_hip(fused, latent, xyz, g_feat, ns=1):
+    """d loss / d latent (K, C, H, W), K = scenes * ns maps, from the looked-up features' gradient g_feat (K * B
+    rows, or None: nothing passes through the lookup) on HIP: avr_latent_features_adjoint writes (K, H*W, C),
+    returned as its (K, C, H, W) view (channels-last strides: no transpose pass; the encoder's backward takes it).
+    Deterministic, unlike torch's grid_sampler_2d_backward (float atomics)."""
+    K, C, H, W = latent.shape
+    if g_feat is None:
+        return torch.zeros_like(latent)
+    with torch.no_grad():
+        p = xyz.detach().to(F32)
+        p = (p.repeat_interleave(ns, 0) if ns > 1 else p).contiguous()
+        d_hwc = ops.latent_features_adjoint(fused.views(range(K), ns), p, g_feat, (H, W))
+    return d_hwc.reshape(K, H, W, C).permute(0, 3, 1, 2)
+
+
+def input_grads(fused, xyz, viewdirs, latent, want_latent, want_xyz, g_feat, g_zf, ns=1):
+    """(d_latent, d_xyz) from the gradients at the MLP inputs (g_feat, g_zf as input_grads_via_autograd): the
+    latent maps' on HIP where latent_grad_on_hip, whatever remains through torch autograd. Records which in
+    fused.last_latent_grad ("hip" | "autograd") when the maps want a gradient."""
+    d_latent = None
+    if want_latent:
+        hip = latent_grad_on_hip(latent, xyz.shape[0] * ns)
+        fused.last_latent_grad = "hip" if hip else "autograd"
+        if hip:
+            d_latent, want_latent = latent_grad_hip(fused, latent, xyz, g_feat, ns), False
+    d_lat, d_xyz = input_grads_via_autograd(fused.net, xyz, viewdirs, latent, want_latent, want_xyz, g_feat, g_zf)
+    return (d_latent if d_latent is not None else d_lat), d_xyz
 
 
 def input_grads_via_autograd(net, xyz, viewdirs, latent, want_latent, want_xyz, g_feat, g_zf):

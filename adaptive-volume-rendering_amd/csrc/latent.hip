@@ -295,3 +295,409 @@ extern "C" int avr_zfeature_grad_points(const avr_view_desc* views, int n_scenes
                                                           accumulate ? 1 : 0, grad_xyz);
   return check_launch("zfeature_grad_points_kernel");
 }
+
+// ---- d loss / d latent map: the lookup's adjoint onto the maps (torch's grid_sample input gradient: bilinear,
+// border padding, align_corners=True), channels-last, with no float atomics and a sum order that depends on the
+// inputs alone. An inverted index and a per-destination sum:
+//   1. rank     one wave per kAdjBlockPoints consecutive points of a scene, 64 at a time in point order: the
+//               point's key is its nw texel (bilinear_at's tex[0]); lanes of one key take consecutive ranks from
+//               the (scene, block, texel) counter. Only this wave touches that counter row, batch after batch, so
+//               the integer atomicAdd (used for its coherent read-modify-write) leaves a rank that is the number
+//               of earlier points of the block in the same texel.
+//   2. columns  per (scene, texel): exclusive prefix of the counters over the blocks, and the texel's count.
+//   3. offsets  one workgroup: exclusive scans over the texels of the counts (list starts), of every
+//               destination's chunk count and of its partial-row count (destinations of more than one chunk).
+//   4. place    order[start + block prefix + rank] = point: each texel's list in ascending point index.
+//   5. gather   one wave per (destination texel, chunk of kAdjChunk rows): walks the lists of cells (y, x),
+//               (y, x-1), (y-1, x), (y-1, x-1), recomputes each point's Bilinear and adds w_k * grad row for the
+//               corners k whose texel is the destination; 4 channels per lane per 256-channel group, fp32. A
+//               destination of one chunk writes its row of the map, the others a partial row in scratch.
+//   6. reduce   adds a chunked destination's partial rows in chunk order.
+namespace avr {
+
+constexpr int kAdjChunk = AVR_LATENT_ADJOINT_CHUNK;
+constexpr int kAdjBlockPoints = 1024;
+constexpr int kAdjScanThreads = 1024;
+
+__device__ __forceinline__ int adj_key(const View& v, const float* __restrict__ p) {
+  const int t = bilinear_at(v, p[0], p[1], p[2]).tex[0];
+  const int last = v.H * v.W - 1;
+  return t < 0 ? 0 : (t > last ? last : t);   // the forward's texel always lies inside: this only guards the stores
+}
+
+__global__ void __launch_bounds__(64) latent_adjoint_rank_kernel(LatBatch vb, const float* __restrict__ xyz,
+                                                                 int64_t n_points, int n_blocks,
+                                                                 int* __restrict__ table, int* __restrict__ keys,
+                                                                 int* __restrict__ ranks) {
+  const int lane = threadIdx.x;
+  const int s = blockIdx.y, b = blockIdx.x;
+  const View& v = vb.v[s];
+  const int hw = v.H * v.W;
+  int* T = table + ((int64_t)s * n_blocks + b) * hw;
+  const int64_t m0 = (int64_t)b * kAdjBlockPoints;
+  const int64_t m1 = m0 + kAdjBlockPoints < n_points ? m0 + kAdjBlockPoints : n_points;
+  for (int64_t base = m0; base < m1; base += 64) {
+    const int64_t m = base + lane;
+    const bool act = m < m1;
+    const int64_t row = s * n_points + m;
+    const int key = act ? adj_key(v, xyz + 3 * row) : -1;
+    // the lanes of one key: their first lane (the leader), their number, each lane's place among them
+    int leader = lane, members = 0, place = 0;
+    uint64_t todo = __ballot(act);
+    while (todo) {
+      const int first = __ffsll((unsigned long long)todo) - 1;
+      const int k = __shfl(key, first, 64);
+      const uint64_t grp = __ballot(act && key == k);
+      if (act && key == k) {
+        leader = first;
+        members = __popcll(grp);
+        place = __popcll(grp & ((1ull << lane) - 1ull));
+      }
+      todo &= ~grp;
+    }
+    // one round trip per batch: every leader advances its key's counter (distinct addresses) and hands the old
+    // value to its lanes
+    int off = 0;
+    if (act && lane == leader) off = atomicAdd(&T[key], members);
+    off = __shfl(off, leader, 64);
+    if (act) {
+      keys[row] = key;
+      ranks[row] = off + place;
+    }
+  }
+}
+
+__global__ void __launch_bounds__(256) latent_adjoint_columns_kernel(int n_texels, int hw, int n_blocks,
+                                                                     int* __restrict__ table,
+                                                                     int* __restrict__ count) {
+  const int gid = blockIdx.x * 256 + threadIdx.x;
+  if (gid >= n_texels) return;
+  const int s = gid / hw, t = gid - s * hw;
+  int* col = table + (int64_t)s * n_blocks * hw + t;
+  int run = 0;
+  for (int b = 0; b < n_blocks; ++b) {
+    const int c = col[(int64_t)b * hw];
+    col[(int64_t)b * hw] = run;
+    run += c;
+  }
+  count[gid] = run;
+}
+
+// rows of destination gid's walk: the lists of its own cell and of the cells left, above and above-left of it
+__device__ __forceinline__ int adj_walk_rows(const int* __restrict__ count, int gid, int hw, int W) {
+  const int t = gid % hw, y = t / W, x = t - y * W;
+  int n = count[gid];
+  if (x > 0) n += count[gid - 1];
+  if (y > 0) n += count[gid - W];
+  if (x > 0 && y > 0) n += count[gid - W - 1];
+  return n;
+}
+
+__device__ __forceinline__ int adj_chunks(int rows) { return rows <= kAdjChunk ? 1 : (rows + kAdjChunk - 1) / kAdjChunk; }
+
+// start / chunk0 / pchunk0: n_texels + 1 entries each (the last one the total)
+__global__ void __launch_bounds__(kAdjScanThreads) latent_adjoint_offsets_kernel(int n_texels, int hw, int W,
+                                                                                 const int* __restrict__ count,
+                                                                                 int* __restrict__ start,
+                                                                                 int* __restrict__ chunk0,
+                                                                                 int* __restrict__ pchunk0) {
+  __shared__ int wave_sums[3][kAdjScanThreads / 64];
+  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  int carry[3] = {0, 0, 0};
+  // 1024 texels per pass (coalesced reads): a shuffle scan per wave, the waves' totals through LDS, a running carry
+  for (int tile = 0; tile < n_texels; tile += kAdjScanThreads) {
+    const int g = tile + tid;
+    int v[3] = {0, 0, 0};
+    if (g < n_texels) {
+      const int nc = adj_chunks(adj_walk_rows(count, g, hw, W));
+      v[0] = count[g];
+      v[1] = nc;
+      v[2] = nc > 1 ? nc : 0;
+    }
+    int inc[3] = {v[0], v[1], v[2]};
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+#pragma unroll
+      for (int k = 0; k < 3; ++k) {
+        const int o = __shfl_up(inc[k], d, 64);
+        if (lane >= d) inc[k] += o;
+      }
+    }
+    if (lane == 63) {
+#pragma unroll
+      for (int k = 0; k < 3; ++k) wave_sums[k][wid] = inc[k];
+    }
+    __syncthreads();
+    int before[3] = {0, 0, 0}, total[3] = {0, 0, 0};
+    for (int w = 0; w < kAdjScanThreads / 64; ++w) {
+#pragma unroll
+      for (int k = 0; k < 3; ++k) {
+        const int t = wave_sums[k][w];
+        before[k] += w < wid ? t : 0;
+        total[k] += t;
+      }
+    }
+    if (g < n_texels) {
+      start[g] = carry[0] + before[0] + inc[0] - v[0];
+      chunk0[g] = carry[1] + before[1] + inc[1] - v[1];
+      pchunk0[g] = carry[2] + before[2] + inc[2] - v[2];
+    }
+#pragma unroll
+    for (int k = 0; k < 3; ++k) carry[k] += total[k];
+    __syncthreads();
+  }
+  if (tid == 0) { start[n_texels] = carry[0]; chunk0[n_texels] = carry[1]; pchunk0[n_texels] = carry[2]; }
+}
+
+__global__ void __launch_bounds__(256) latent_adjoint_place_kernel(int64_t n_rows, int64_t n_points, int hw,
+                                                                   int n_blocks, const int* __restrict__ keys,
+                                                                   const int* __restrict__ ranks,
+                                                                   const int* __restrict__ table,
+                                                                   const int* __restrict__ start,
+                                                                   int* __restrict__ order) {
+  const int64_t row = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (row >= n_rows) return;
+  const int64_t s = row / n_points, m = row - s * n_points;
+  const int key = keys[row];
+  const int64_t b = m / kAdjBlockPoints;
+  const int64_t pos = (int64_t)start[s * hw + key] + table[(s * n_blocks + b) * hw + key] + ranks[row];
+  if (pos >= 0 && pos < n_rows) order[pos] = (int)m;
+}
+
+__global__ void __launch_bounds__(256) latent_adjoint_gather_kernel(LatBatch vb, const float* __restrict__ xyz,
+                                                                    int64_t n_points, const float* __restrict__ grad,
+                                                                    int64_t ldg, int C, int n_texels,
+                                                                    const int* __restrict__ count,
+                                                                    const int* __restrict__ start,
+                                                                    const int* __restrict__ chunk0,
+                                                                    const int* __restrict__ pchunk0,
+                                                                    const int* __restrict__ order,
+                                                                    int64_t max_partials, float* __restrict__ partial,
+                                                                    float* __restrict__ out) {
+  const int lane = threadIdx.x & 63;
+  const int w = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * 4 + (threadIdx.x >> 6)));
+  if (w >= chunk0[n_texels]) return;
+  // the destination: the last texel whose first chunk is at or before w (every texel has at least one chunk)
+  int lo = 0, hi = n_texels - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (chunk0[mid] <= w) lo = mid; else hi = mid - 1;
+  }
+  const int gid = __builtin_amdgcn_readfirstlane(lo);
+  const int j = w - chunk0[gid], n_chunks = chunk0[gid + 1] - chunk0[gid];
+  const int W = vb.v[0].W, hw = vb.v[0].H * W;
+  const int s = gid / hw, t = gid - s * hw, y = t / W, x = t - y * W;
+  const View& v = vb.v[s];
+  float* dst;
+  if (n_chunks == 1) {
+    dst = out + (int64_t)gid * C;
+  } else {
+    const int64_t p = (int64_t)pchunk0[gid] + j;
+    if (p >= max_partials) return;   // cannot happen (the bound is proved at the scratch layout): guards the store
+    dst = partial + p * C;
+  }
+  const int r0 = j * kAdjChunk, r1 = r0 + kAdjChunk;   // this wave's rows of the destination's walk
+  xyz += 3 * (int64_t)s * n_points;
+  grad += (int64_t)s * n_points * ldg;
+  // the walk: the lists of the four cells one after the other, cell q's rows at [vend[q], vend[q + 1]) of it
+  int cstart[4], vend[5];
+  vend[0] = 0;
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    const int dx = q & 1, dy = q >> 1;
+    const bool there = x - dx >= 0 && y - dy >= 0;
+    const int cell = there ? gid - dy * W - dx : gid;
+    cstart[q] = __builtin_amdgcn_readfirstlane(start[cell]);
+    vend[q + 1] = vend[q] + (there ? __builtin_amdgcn_readfirstlane(count[cell]) : 0);
+  }
+  const int e = r1 < vend[4] ? r1 : vend[4];
+  for (int cb = 0; cb < C; cb += 1024) {
+    floatx4 acc[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) acc[u] = floatx4{0.f, 0.f, 0.f, 0.f};
+    for (int i = r0; i < e; i += 64) {
+      const int nb = e - i < 64 ? e - i : 64;
+      // lane l: row i + l of the walk -- its point and the weight it gives this texel (0 and point 0 past nb)
+      int m = 0;
+      float wt = 0.f;
+      if (lane < nb) {
+        const int vi = i + lane;
+        const int pos = vi < vend[1] ? cstart[0] + vi
+                                     : (vi < vend[2] ? cstart[1] + vi - vend[1]
+                                                     : (vi < vend[3] ? cstart[2] + vi - vend[2] : cstart[3] + vi - vend[3]));
+        m = order[pos];
+        m = m < 0 ? 0 : (m < n_points ? m : (int)n_points - 1);   // a point index by construction: guards the reads
+        const Bilinear bl = bilinear_at(v, xyz[3 * (int64_t)m], xyz[3 * (int64_t)m + 1], xyz[3 * (int64_t)m + 2]);
+        // a corner clamped onto its neighbour carries an exact zero weight, so this sum is the one live weight
+#pragma unroll
+        for (int k = 0; k < 4; ++k) wt += bl.tex[k] == t ? bl.w[k] : 0.f;
+      }
+      // four rows' loads in flight before their sums (a row past nb reads point 0's row and is not added)
+      for (int r = 0; r < nb; r += 4) {
+        floatx4 gv[4][4];
+        float wr[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          const int mr = __builtin_amdgcn_readlane(m, r + k);
+          wr[k] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(wt), r + k));
+          const float* g = grad + (int64_t)mr * ldg + cb + 4 * lane;
+#pragma unroll
+          for (int u = 0; u < 4; ++u)
+            if (cb + 4 * lane + 256 * u < C) gv[k][u] = *reinterpret_cast<const floatx4*>(g + 256 * u);
+        }
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          if (r + k < nb) {
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+              if (cb + 4 * lane + 256 * u < C) {
+#pragma unroll
+                for (int z = 0; z < 4; ++z) acc[u][z] = __builtin_fmaf(wr[k], gv[k][u][z], acc[u][z]);
+              }
+            }
+          }
+        }
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const int c = cb + 4 * lane + 256 * u;
+      if (c < C) *reinterpret_cast<floatx4*>(dst + c) = acc[u];
+    }
+  }
+}
+
+__global__ void __launch_bounds__(256) latent_adjoint_reduce_kernel(int C, int n_texels,
+                                                                    const int* __restrict__ chunk0,
+                                                                    const int* __restrict__ pchunk0,
+                                                                    int64_t max_partials,
+                                                                    const float* __restrict__ partial,
+                                                                    float* __restrict__ out) {
+  const int lane = threadIdx.x & 63;
+  const int gid = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (gid >= n_texels) return;
+  const int n_chunks = chunk0[gid + 1] - chunk0[gid];
+  if (n_chunks <= 1) return;
+  const int64_t p0 = pchunk0[gid];
+  if (p0 + n_chunks > max_partials) return;
+  for (int c = 4 * lane; c < C; c += 256) {
+    floatx4 acc = *reinterpret_cast<const floatx4*>(partial + p0 * C + c);
+    for (int j = 1; j < n_chunks; ++j) acc += *reinterpret_cast<const floatx4*>(partial + (p0 + j) * C + c);
+    *reinterpret_cast<floatx4*>(out + (int64_t)gid * C + c) = acc;
+  }
+}
+
+__global__ void __launch_bounds__(256) latent_adjoint_zero_kernel(int64_t n4, floatx4* __restrict__ out) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i < n4) out[i] = floatx4{0.f, 0.f, 0.f, 0.f};
+}
+
+}  // namespace avr
+
+// scratch regions of avr_latent_features_adjoint, 256-B aligned. A destination of more than one chunk walks
+// rows > kAdjChunk rows in ceil(rows / kAdjChunk) < 2 rows / kAdjChunk chunks, and every point is walked by at
+// most 4 destinations: at most 8 n_rows / kAdjChunk partial rows; at most 4 n_rows / kAdjChunk + n_texels chunks.
+struct AdjScratch {
+  int64_t keys, ranks, order, table, count, start, chunk0, pchunk0, partial, total;
+  int64_t n_blocks, max_chunks, max_partials;
+};
+
+static AdjScratch adjoint_scratch(int n_scenes, int64_t n_points, int64_t hw, int channels) {
+  const auto up = [](int64_t b) { return (b + 255) & ~(int64_t)255; };
+  const int64_t n_rows = (int64_t)n_scenes * n_points, n_texels = (int64_t)n_scenes * hw;
+  AdjScratch m;
+  m.n_blocks = (n_points + kAdjBlockPoints - 1) / kAdjBlockPoints;
+  m.max_chunks = 4 * n_rows / kAdjChunk + n_texels;
+  m.max_partials = 8 * n_rows / kAdjChunk;
+  int64_t o = 0;
+  m.keys = o;    o += up(n_rows * 4);
+  m.ranks = o;   o += up(n_rows * 4);
+  m.order = o;   o += up(n_rows * 4);
+  m.table = o;   o += up(n_scenes * m.n_blocks * hw * 4);
+  m.count = o;   o += up(n_texels * 4);
+  m.start = o;   o += up((n_texels + 1) * 4);
+  m.chunk0 = o;  o += up((n_texels + 1) * 4);
+  m.pchunk0 = o; o += up((n_texels + 1) * 4);
+  m.partial = o; o += up(m.max_partials * channels * 4);
+  m.total = o;
+  return m;
+}
+
+static int adjoint_sizes(const char* what, int n_scenes, int64_t n_points, int latent_h, int latent_w, int channels) {
+  AVR_REQUIRE(n_scenes >= 1 && n_scenes <= AVR_MAX_SCENES, "%s: n_scenes %d not in 1..%d", what, n_scenes,
+              AVR_MAX_SCENES);
+  AVR_REQUIRE(latent_h > 0 && latent_w > 0 && (int64_t)latent_h * latent_w * n_scenes < (1ll << 31) / 2,
+              "%s: bad latent size %d x %d", what, latent_h, latent_w);
+  AVR_REQUIRE(channels > 0 && channels % 4 == 0, "%s: channels %d not a positive multiple of 4", what, channels);
+  AVR_REQUIRE(n_points >= 0 && n_points * n_scenes < (1ll << 31) / 8, "%s: n_points %lld out of range", what,
+              (long long)n_points);
+  return AVR_OK;
+}
+
+extern "C" int avr_latent_features_adjoint_scratch_bytes(int n_scenes, int64_t n_points, int latent_h, int latent_w,
+                                                         int channels, int64_t* n_bytes) {
+  AVR_REQUIRE(n_bytes, "avr_latent_features_adjoint_scratch_bytes: null pointer");
+  int rc = adjoint_sizes("avr_latent_features_adjoint_scratch_bytes", n_scenes, n_points, latent_h, latent_w, channels);
+  if (rc) return rc;
+  *n_bytes = adjoint_scratch(n_scenes, n_points, (int64_t)latent_h * latent_w, channels).total;
+  return AVR_OK;
+}
+
+extern "C" int avr_latent_features_adjoint(const avr_view_desc* views, int n_scenes, const float* xyz,
+                                           int64_t n_points, const float* grad_features, int64_t ld_grad,
+                                           int channels, float* grad_latent_hwc, void* scratch,
+                                           int64_t scratch_bytes, void* stream) {
+  const char* what = "avr_latent_features_adjoint";
+  AVR_REQUIRE(n_scenes >= 1 && n_scenes <= AVR_MAX_SCENES, "%s: n_scenes %d not in 1..%d", what, n_scenes,
+              AVR_MAX_SCENES);
+  AVR_REQUIRE(views && grad_latent_hwc && scratch && ((xyz && grad_features) || n_points == 0), "%s: null pointer",
+              what);
+  LatBatch vb;
+  int rc = lookup_views(views, n_scenes, &vb, what);
+  if (rc) return rc;
+  rc = adjoint_sizes(what, n_scenes, n_points, views[0].latent_h, views[0].latent_w, channels);
+  if (rc) return rc;
+  AVR_REQUIRE(ld_grad >= channels, "%s: ld_grad %lld < channels %d", what, (long long)ld_grad, channels);
+  AVR_REQUIRE(ld_grad % 4 == 0 && (uintptr_t)grad_features % 16 == 0 && (uintptr_t)grad_latent_hwc % 16 == 0 &&
+                  (uintptr_t)scratch % 16 == 0,
+              "%s: rows not 16-B aligned", what);
+  const int hw = views[0].latent_h * views[0].latent_w;
+  const AdjScratch m = adjoint_scratch(n_scenes, n_points, hw, channels);
+  AVR_REQUIRE(scratch_bytes >= m.total, "%s: scratch of %lld bytes < %lld", what, (long long)scratch_bytes,
+              (long long)m.total);
+  hipStream_t st = as_stream(stream);
+  const int n_texels = n_scenes * hw;
+  const int64_t n_rows = (int64_t)n_scenes * n_points;
+  if (n_points == 0) {
+    const int64_t n4 = (int64_t)n_texels * channels / 4;
+    latent_adjoint_zero_kernel<<<dim3((unsigned)((n4 + 255) / 256)), 256, 0, st>>>(
+        n4, reinterpret_cast<floatx4*>(grad_latent_hwc));
+    return check_launch("latent_adjoint_zero_kernel");
+  }
+  char* sb = static_cast<char*>(scratch);
+  int* keys = reinterpret_cast<int*>(sb + m.keys);
+  int* ranks = reinterpret_cast<int*>(sb + m.ranks);
+  int* order = reinterpret_cast<int*>(sb + m.order);
+  int* table = reinterpret_cast<int*>(sb + m.table);
+  int* count = reinterpret_cast<int*>(sb + m.count);
+  int* start = reinterpret_cast<int*>(sb + m.start);
+  int* chunk0 = reinterpret_cast<int*>(sb + m.chunk0);
+  int* pchunk0 = reinterpret_cast<int*>(sb + m.pchunk0);
+  float* partial = reinterpret_cast<float*>(sb + m.partial);
+  if (hipMemsetAsync(table, 0, (size_t)n_scenes * m.n_blocks * hw * 4, st) != hipSuccess)
+    return check_launch("avr_latent_features_adjoint: clearing the counters");
+  latent_adjoint_rank_kernel<<<dim3((unsigned)m.n_blocks, (unsigned)n_scenes), 64, 0, st>>>(
+      vb, xyz, n_points, (int)m.n_blocks, table, keys, ranks);
+  latent_adjoint_columns_kernel<<<dim3((unsigned)((n_texels + 255) / 256)), 256, 0, st>>>(n_texels, hw, (int)m.n_blocks,
+                                                                                        table, count);
+  latent_adjoint_offsets_kernel<<<1, kAdjScanThreads, 0, st>>>(n_texels, hw, views[0].latent_w, count, start, chunk0,
+                                                               pchunk0);
+  latent_adjoint_place_kernel<<<dim3((unsigned)((n_rows + 255) / 256)), 256, 0, st>>>(
+      n_rows, n_points, hw, (int)m.n_blocks, keys, ranks, table, start, order);
+  latent_adjoint_gather_kernel<<<dim3((unsigned)((m.max_chunks + 3) / 4)), 256, 0, st>>>(
+      vb, xyz, n_points, grad_features, ld_grad, channels, n_texels, count, start, chunk0, pchunk0, order,
+      m.max_partials, partial, grad_latent_hwc);
+  latent_adjoint_reduce_kernel<<<dim3((unsigned)((n_texels + 3) / 4)), 256, 0, st>>>(
+      channels, n_texels, chunk0, pchunk0, m.max_partials, partial, grad_latent_hwc);
+  return check_launch("avr_latent_features_adjoint");
+}

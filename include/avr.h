@@ -507,6 +507,27 @@ int avr_latent_tables_grad_points(const avr_view_desc* views, int n_scenes, cons
 int avr_zfeature_grad_points(const avr_view_desc* views, int n_scenes, const float* xyz, int64_t n_points,
                              const float* grad_zf, int64_t ld_grad, int num_freqs, float freq_factor, int accumulate,
                              float* grad_xyz, void* stream);
+/* An addition within ABI 18: the adjoint of the batched lookup with respect to the maps -- grid_sample's input
+ * gradient (bilinear, border padding, align_corners=True), channels-last like latent_hwc:
+ *   grad_latent_hwc[s, t, :] = sum over points m of scene s and corners k with tex_k(m) == t of
+ *                              w_k(m) * grad_features[s * n_points + m, :]
+ * with (tex, w) the forward's corners and weights (a clamped corner keeps its zero weight). views / xyz as
+ * avr_latent_features_batch; grad_features rows s * n_points + m of ld_grad >= channels floats; grad_latent_hwc
+ * (n_scenes, H*W, channels), every row written (zeros where no point lands: no memset needed; n_points = 0 writes
+ * a zero map). No float atomics and no data-dependent sum order, so a call is bit-reproducible: the points are
+ * ordered stably by (scene, nw texel) -- integer counting, equal texels in ascending point index -- and one wave
+ * per destination texel sums the rows of its four neighbouring cells in that order, in chunks of
+ * AVR_LATENT_ADJOINT_CHUNK rows whose partial rows (chunk order) a short pass adds. Nothing is read back to the
+ * host: grids and scratch are sized by bounds. `scratch` holds avr_latent_features_adjoint_scratch_bytes(...)
+ * bytes (monotone in n_points), 16-B aligned like grad_features, its rows (ld_grad a multiple of 4) and
+ * grad_latent_hwc; channels a multiple of 4; n_scenes * n_points < 2^28. xyz and grad_features may be NULL when
+ * n_points = 0. A bad argument returns AVR_E_INVALID before any launch.                                           */
+#define AVR_LATENT_ADJOINT_CHUNK 512
+int avr_latent_features_adjoint_scratch_bytes(int n_scenes, int64_t n_points, int latent_h, int latent_w,
+                                              int channels, int64_t* n_bytes);
+int avr_latent_features_adjoint(const avr_view_desc* views, int n_scenes, const float* xyz, int64_t n_points,
+                                const float* grad_features, int64_t ld_grad, int channels,
+                                float* grad_latent_hwc, void* scratch, int64_t scratch_bytes, void* stream);
 
 /* --------------------------------------------------------- LSTM ray marcher
  * Raymarcher / AdaptiveVolumeRenderer march (renderers.py:313-351, :380-432):
