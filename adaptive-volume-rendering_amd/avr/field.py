@@ -8,26 +8,27 @@ parameter or the latent changes (tensor version counters), so an inference
 loop over many frames of one scene pays for them once, as the reference pays
 for encode() once.
 
-Every cache entry is one _Record(key, value, keep, stamp) behind _cached: a hit under the same key joins the
-reading stream to the maker's (_join), a miss builds, stamps (_stamp) and stores. A packed blob (_Packed) declares
-what hangs off it (backward blob, per-scene and batched lin_z tables) and hands each library call a by-value copy
-of its dims for the kernel precision the call means (dims_as): the cached struct is never written. _FieldTrain
-shares its entry, latent lookup and autograd tail with avr.bn_train / avr.layer_train (avr.train_common).
+Every cache entry goes through avr.cache's one protocol (_Record, _cached) under keys built from that module's
+counters. A packed blob (_Packed) declares what hangs off it (backward blob, per-scene and batched lin_z tables) and
+hands each library call a by-value copy of its dims for the kernel precision the call means (dims_as): the cached
+struct is never written. _FieldTrain shares its entry, latent lookup and autograd tail with avr.bn_train /
+avr.layer_train (avr.train_common).
 """
-import collections
 import ctypes
+import operator
 import os
-import typing
 import weakref
 
 import torch
-from torch.optim.optimizer import register_optimizer_step_post_hook
 
 from . import _lib, ops, train_common
 from ._lib import FieldDims, ResnetFCWeights, ViewDesc, call, ptr, require_device, scene_groups, stream_of
+from .cache import (_EXPLICIT_GEN, _MODULE_GEN, _PARAM_GEN, _Record, _cached, _hit, _slot_current, _stamp, _version_key,
+                    bump_param_generation, param_generation)   # noqa: F401 (the last two: this module's API too)
 from .train_common import input_grads, latent_grad_hip, latent_grad_on_hip, lookup_features
 
 F32 = torch.float32
+_blob = operator.attrgetter("packed")   # the device tensor of a _Packed: what its record's stamp marks
 
 
 def uses_bn(mlp):
@@ -122,118 +123,6 @@ def _freq_factor(code):
     return float(ff)
 
 
-# Submodule (re)registrations anywhere in the process, numbered, with the id of the module that registered: a
-# FusedField._state slot is rebuilt after a registration under its MLP, so a module replaced in an MLP
-# (mlp.lin_in = nn.Linear(...)) is seen, and only then (modules built elsewhere, e.g. per training step, leave it
-# alone); parameters and buffers replaced in place are read through their owners' dicts anyway.
-_MODULE_GEN = [0]
-_REG_LOG = collections.deque(maxlen=4096)   # (generation, id(parent module))
-
-
-def _module_registered(module, name, submodule):
-    _MODULE_GEN[0] += 1
-    _REG_LOG.append((_MODULE_GEN[0], id(module)))
-
-
-def _slot_current(gen, module_ids):
-    """No registration since generation `gen` under a module of module_ids (the log must still cover them all;
-    a reused id only costs a rebuild)."""
-    if gen == _MODULE_GEN[0]:
-        return True
-    if not _REG_LOG or _REG_LOG[0][0] > gen + 1:
-        return False
-    return not any(pid in module_ids for g, pid in _REG_LOG if g > gen)
-
-
-torch.nn.modules.module.register_module_module_registration_hook(_module_registered)
-
-
-# Every optimizer step anywhere in the process, counted: a fused optimizer (torch.optim.Adam(fused=True)) updates
-# the parameters in one multi-tensor kernel without advancing their version counters, so the (data_ptr, _version)
-# keys of the caches below would not see it (the blob would keep the old weights). The count is part of every key;
-# GraphedTrainStep advances it after each replay (a captured optimizer step runs no host hook).
-_PARAM_GEN = [0]
-_EXPLICIT_GEN = [0]   # bump_param_generation() calls alone: the key of latent maps no optimizer can hold
-
-
-def _optimizer_stepped(optimizer, args, kwargs):
-    _PARAM_GEN[0] += 1
-
-
-register_optimizer_step_post_hook(_optimizer_stepped)
-
-
-def bump_param_generation():
-    """Invalidate every FusedField cache entry derived from parameters or the latent map (after an update the
-    version counters do not record: a replayed optimizer step, a write through .data)."""
-    _PARAM_GEN[0] += 1
-    _EXPLICIT_GEN[0] += 1
-
-
-def param_generation():
-    return _PARAM_GEN[0]
-
-
-def _version_key(tensors, gen=True):
-    """(data_ptr, _version) of each tensor, with the optimizer-step generation for anything an optimizer may
-    update (gen=False: the source views -- poses, focal, principal point -- which none does)."""
-    return ((_PARAM_GEN[0],) if gen else ()) + tuple((t.data_ptr(), t._version) for t in tensors)
-
-
-def _stamp(t):
-    """(stream, event) marking the current stream's work that filled the cached device tensor t. None on the CPU,
-    and None while a HIP graph is being captured: a value made during a capture is read without a join, also by
-    the adaptive renderer's side stream inside the graph (the open ADVICE.md finding; its fix is here and in _join)."""
-    if t is None or not t.is_cuda or torch.cuda.is_current_stream_capturing():
-        return None
-    s = torch.cuda.current_stream(t.device)
-    ev = torch.cuda.Event()
-    ev.record(s)
-    return s, ev
-
-
-def _join(stamp, *tensors):
-    """A cached value read from another stream than the one that made it (the adaptive renderer's side stream,
-    avr.renderers): that stream waits for the maker's work, and the tensors' memory is kept from reuse under the
-    maker's later allocations until this stream's work on them is done."""
-    if stamp is None:
-        return
-    s = torch.cuda.current_stream(stamp[0].device)
-    if s == stamp[0]:
-        return
-    s.wait_event(stamp[1])
-    for t in tensors:
-        if t is not None and t.is_cuda:
-            t.record_stream(s)
-
-
-class _Record(typing.NamedTuple):
-    """One cache entry: the comparable key it was built under, the value, whatever must stay alive for the key
-    to stay sound (a tensor whose address is part of it), and the _stamp of the value's maker."""
-    key: object
-    value: object
-    keep: object = None
-    stamp: object = None
-
-
-def _hit(rec, key):
-    """True when rec holds a value built under `key`; the current stream is then joined to its maker's."""
-    if rec is None or rec.key != key:
-        return False
-    _join(rec.stamp, rec.value)
-    return True
-
-
-def _cached(store, slot, key, make, keep=None, device=True):
-    """store[slot]'s value if it was built under `key`, else make() stored in its place (the cache protocol of
-    every FusedField cache; device=False: a host-side value, nothing to stamp or join)."""
-    rec = store.get(slot)
-    if not _hit(rec, key):
-        value = make()
-        rec = store[slot] = _Record(key, value, keep, _stamp(value) if device else None)
-    return rec.value
-
-
 PRECISIONS = {"fp32": _lib.FIELD_FP32, "x3": _lib.FIELD_X3}
 
 
@@ -275,13 +164,11 @@ class FusedField:
         # how the last training backward formed d loss / d latent: "hip" (avr_latent_features_adjoint) | "autograd"
         # (torch's grid_sample adjoint), None before the first (for tests / introspection, as renderers' last_path)
         self.last_latent_grad = None
-        # the caches: slot -> _Record, read and filled by _cached (packed() alone keeps its own body)
+        # the caches: slot -> _Record, read and filled by _cached
         self._packed = {}         # coarse, or (coarse, "bn_train") -> _Record of a _Packed (tables hang off it)
-        self._view_cache = {}     # (sb, ns) -> ViewDesc (view())
-        self._views_cache = {}    # (range, ns) -> ViewDesc arrays (views())
+        self._view_cache = {}     # (sb, ns) -> ViewDesc (view()); (range, ns) -> ViewDesc arrays (views())
         self._latent_cache = {}   # per latent version: channels-last copies, max |latent| (both MLPs share them)
-        # not a _Record: the last build's pack arguments, reused while the weight pointers stay (packed())
-        self._pack_args = {}      # slot of _packed -> (pointer key, blob floats, ResnetFCWeights, kept tensors)
+        self._pack_args = {}      # slot of _packed -> the last build's _pack_weights(), reused while the pointers stay
         # mlp (weakly) -> ([(name, owner dict, key)] params, [...] float buffers, generation, ids of its modules)
         self._slots = weakref.WeakKeyDictionary()
 
@@ -294,7 +181,6 @@ class FusedField:
         self._pack_args.clear()
         if views:
             self._view_cache.clear()
-            self._views_cache.clear()
         self._latent_cache.clear()
 
     def cache_tensors(self):
@@ -302,21 +188,17 @@ class FusedField:
         what a captured HIP graph reads (avr.graphs.GraphedRenderer keeps references to them, so an eager call
         that replaces a cache entry cannot free memory a replay still reads)."""
         out = []
-        for rec in self._packed.values():
-            entry = rec[1]
-            if entry is None:
-                continue
-            out.append(entry.packed)
-            if entry.bwd is not None:
-                out.append(entry.bwd.value)
-            out += [r.value for r in entry.tables.values()]
-            out += [r.value for r in entry.batch_tables.values()]
+        for entry in (rec[1] for rec in self._packed.values() if rec[1] is not None):
+            recs = [entry.bwd, *entry.tables.values(), *entry.batch_tables.values()]
+            out += [entry.packed] + [r.value for r in recs if r is not None]
         return out
 
     def _latent_cached(self, what, latent, make):
-        # the optimizer-step count matters only for a latent an optimizer can hold (a leaf that requires grad): a
-        # fixed or encoder-produced map keeps its copies across steps (its version counter sees in-place writes)
-        gen = _PARAM_GEN[0] if (latent.is_leaf and latent.requires_grad) else (-1, _EXPLICIT_GEN[0])
+        # the optimizer-step count matters only for a latent an optimizer can hold: a leaf that requires grad, or a
+        # view of one (param[idx] shares the leaf's storage, which a fused optimizer updates past every version
+        # counter). A fixed or encoder-produced map keeps its copies across steps (in-place writes advance its version)
+        held = any(t is not None and t.is_leaf and t.requires_grad for t in (latent, latent._base))
+        gen = _PARAM_GEN[0] if held else (-1, _EXPLICIT_GEN[0])
         key = (gen, latent.data_ptr(), latent._version, tuple(latent.shape))
         return _cached(self._latent_cache, what, key, make, keep=latent)   # held: its address is in the key
 
@@ -378,32 +260,23 @@ class FusedField:
         # (avr_field_pack), and net.fused() switches a FusedField's precision in place
         slot = coarse if bn_fold else (coarse, "bn_train")
         key = (id(mlp), self.precision if bn_fold else "x3", _version_key(params))
-        rec = self._packed.get(slot)
-        if rec is not None and rec.key == key:
-            _join(rec.stamp, rec.value.packed)
-            return rec.value
-        dims = self.dims(mlp)
-        if not bn_fold:
-            dims.bn, dims.precision = 0, _lib.FIELD_X3
-        # an optimizer step updates the parameters in place: the same tensors at the same addresses, so the last
-        # build's weight pointers, blob size and kept tensors serve again and only the pack launch reruns (when
-        # every pointer was a parameter or buffer read in place; derived tensors -- the eval-BN folds, dtype
-        # conversions -- are rebuilt every time)
-        args_key = (id(mlp), tuple(pv[0] for pv in key[2][1:]), bytes(dims))
-        args = self._pack_args.get(slot)
-        if args is not None and args[0] == args_key:
-            _, n, w, keep = args
-        else:
-            n, w, keep, in_place = self._pack_weights(mlp, dims)
-            if in_place:
-                self._pack_args[slot] = (args_key, n, w, keep)
-            else:
-                self._pack_args.pop(slot, None)
-        packed = torch.empty(n, device=params[0].device, dtype=F32)
-        call("avr_field_pack", ctypes.byref(dims), ctypes.byref(w), ptr(packed), stream_of(packed))
-        entry = _Packed(dims, packed, w, keep)
-        self._packed[slot] = _Record(key, entry, None, _stamp(packed))
-        return entry
+
+        def make():
+            dims = self.dims(mlp)
+            if not bn_fold:
+                dims.bn, dims.precision = 0, _lib.FIELD_X3
+            # an optimizer step updates the parameters in place: same tensors, same addresses, so the last build's
+            # weight pointers, blob size and kept tensors serve again and only the pack launch reruns (when every
+            # pointer was a parameter or buffer read in place; derived tensors -- BN folds, conversions -- are rebuilt)
+            args_key = (id(mlp), tuple(pv[0] for pv in key[2][1:]), bytes(dims))
+            n, w, keep, in_place = _cached(self._pack_args, slot, args_key, lambda: self._pack_weights(mlp, dims),
+                                           device=False)
+            if not in_place:
+                del self._pack_args[slot]
+            packed = torch.empty(n, device=params[0].device, dtype=F32)
+            call("avr_field_pack", ctypes.byref(dims), ctypes.byref(w), ptr(packed), stream_of(packed))
+            return _Packed(dims, packed, w, keep)
+        return _cached(self._packed, slot, key, make, of=_blob)
 
     def _pack_weights(self, mlp, dims):
         """avr_field_pack's arguments for mlp: (blob floats, weight pointers, the tensors behind them, whether every
@@ -529,7 +402,7 @@ class FusedField:
         under one source-version key (per-view keys for every scene of every launch were host time)."""
         srcs = self._view_sources()
         key = (_version_key(srcs, gen=False), tuple(self.net.encoder.latent.shape))
-        return _cached(self._views_cache, (idx.start, idx.stop, idx.step, ns), key,
+        return _cached(self._view_cache, (idx.start, idx.stop, idx.step, ns), key,
                        lambda: (ViewDesc * len(idx))(*[self.view(i, ns) for i in idx]), keep=srcs, device=False)
 
     # ----------------------------------------------------------- evaluation

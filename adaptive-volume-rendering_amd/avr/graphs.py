@@ -27,9 +27,16 @@ after that. Warm-ups and re-captures leave the renderer's Philox offset where it
 import torch
 
 from . import anomaly
-from .field import bump_param_generation, param_generation
+from .cache import bump_param_generation, capture_scope, param_generation
 
 __all__ = ["GraphedRenderer", "GraphedTrainStep"]
+
+
+def _net_views(net):
+    """The source-view state net.encode() replaces: latent, latent scaling, poses, focal, principal point."""
+    enc = getattr(net, "encoder", None)
+    return [getattr(enc, "latent", None), getattr(enc, "latent_scaling", None)] + \
+           [getattr(net, a, None) for a in ("poses", "focal", "c", "image_shape")]
 
 
 class GraphedRenderer:
@@ -68,10 +75,7 @@ class GraphedRenderer:
         return ts
 
     def _views(self):
-        """The source-view state net.encode() replaces: latent, latent scaling, poses, focal, principal point."""
-        enc = getattr(self.net, "encoder", None)
-        return [getattr(enc, "latent", None), getattr(enc, "latent_scaling", None)] + \
-               [getattr(self.net, a, None) for a in ("poses", "focal", "c", "image_shape")]
+        return _net_views(self.net)
 
     def _stale(self):
         # held references: no address is reused while compared
@@ -101,7 +105,7 @@ class GraphedRenderer:
         torch.cuda.current_stream().wait_stream(stream)
         renderer._offset = self.offset = offset0
         self.graph = torch.cuda.CUDAGraph()
-        with torch.no_grad(), torch.cuda.graph(self.graph):
+        with torch.no_grad(), capture_scope(), torch.cuda.graph(self.graph):
             self.out = renderer(self.c2w, self.K, self.x_pix, net)
         renderer._offset = offset0   # the captured launches keep the offset they were recorded with
         # the packed weights, lin_z tables and batched tables the captured kernels read: referenced here, so an
@@ -185,16 +189,11 @@ class GraphedTrainStep:
         self.warmup = warmup
         self.calls = 0
         self.captures = 0
-        self.graph = None
-        self.out = None
+        self.graph = self.out = None
+        self._eager_until = 0   # the last call that runs eagerly after a change of views (__call__)
 
     def _views(self):
-        out = []
-        for net in self.nets:
-            enc = getattr(net, "encoder", None)
-            out += [getattr(enc, "latent", None), getattr(enc, "latent_scaling", None)]
-            out += [getattr(net, a, None) for a in ("poses", "focal", "c", "image_shape")]
-        return [t for t in out if isinstance(t, torch.Tensor)]
+        return [t for net in self.nets for t in _net_views(net) if isinstance(t, torch.Tensor)]
 
     def _stale(self):
         views = self._views()
@@ -209,7 +208,7 @@ class GraphedTrainStep:
             if fused is not None:
                 fused.invalidate(views=False)   # every blob / table the step reads is made inside the graph
         graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(graph):
+        with capture_scope(), torch.cuda.graph(graph):   # what the step caches is stream-ordered inside the graph
             out = self.step_fn()
         self.graph, self.out = graph, self._detach(out)
         self._held = [(t, t._version) for t in self._views()]
@@ -223,7 +222,7 @@ class GraphedTrainStep:
             # cannot), the next one captures again
             self.graph = self.out = None
             self._eager_until = self.calls
-        if self.calls <= max(self.warmup, getattr(self, "_eager_until", 0)):
+        if self.calls <= max(self.warmup, self._eager_until):
             stream = torch.cuda.Stream()
             stream.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(stream):

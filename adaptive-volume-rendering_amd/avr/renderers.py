@@ -19,13 +19,14 @@ Two evaluation modes for the radiance field:
     runs on the HIP kernel with its HIP backward.
 """
 import ctypes
+import os
 from typing import Tuple
 
 import torch
 from torch import nn
 
 from . import _lib, ops
-from .field import param_generation
+from .cache import _cached, param_generation
 
 
 def _noise(shape, like, kind):
@@ -280,8 +281,7 @@ class _LSTMMarch(nn.Module):
         lstm_forget_gate_init(self.lstm)
         self.out_layer = nn.Linear(hidden_size, 1)
         self.counter = 0
-        self._gate_cache = None
-        self._gates_cache = None   # the stacked per-scene tables of a multi-scene inference call
+        self._gates = {}          # scene count -> avr.cache._Record of the (SB, H*W, 64) gate tables (_gate_tables)
         self.last_path = None
         # None: the reference's draws (CPU normal_, torch.rand); int: in-kernel Philox (inference on the fused path;
         # training keeps the reference's draws)
@@ -289,6 +289,9 @@ class _LSTMMarch(nn.Module):
         self._offset = 0
         self.t_stop = None        # no early termination here (read by avr.graphs.GraphedRenderer)
         self._graph_init = None   # start distances read by a captured training step (stage_host_draws)
+        self._graph_ring = None   # its two pinned staging slots, [host tensor, event of the copy that last read it]
+        self._graph_slot = 0
+        self._side = None         # (device, the side stream of _side_stream)
 
     def _initial_distance(self, SB, num_rays, device, noise):
         if noise is not None and "initial_distance" in noise:
@@ -315,10 +318,9 @@ class _LSTMMarch(nn.Module):
         buf = self._graph_init
         if buf is None:
             return
-        ring = getattr(self, "_graph_ring", None)
+        ring = self._graph_ring
         if ring is None or ring[0][0].shape != buf.shape:
             ring = self._graph_ring = [[torch.empty(buf.shape).pin_memory(), None] for _ in range(2)]
-            self._graph_slot = 0
         slot = ring[self._graph_slot]
         self._graph_slot ^= 1
         if slot[1] is not None:
@@ -331,51 +333,36 @@ class _LSTMMarch(nn.Module):
     def _side_stream(self, phi, world):
         """A second stream of world's device for the marched point's field pass (AdaptiveVolumeRenderer training on
         the HIP path; None otherwise: CPU, inference, the module path, or AVR_ADAPTIVE_SIDE_STREAM=0)."""
-        import os
         if not (world.is_cuda and torch.is_grad_enabled() and getattr(phi, "use_fused", False)
                 and getattr(phi, "hip_backward", False)) or os.environ.get("AVR_ADAPTIVE_SIDE_STREAM") == "0":
             return None
         if torch.cuda.is_current_stream_capturing() and os.environ.get("AVR_ADAPTIVE_SIDE_STREAM_IN_GRAPH") == "0":
             return None
         key = world.device
-        if getattr(self, "_side", None) is None or self._side[0] != key:
+        if self._side is None or self._side[0] != key:
             self._side = (key, torch.cuda.Stream(device=key))
         return self._side[1]
 
-    def _gate_table(self, phi):
+    def _gate_tables(self, phi, SB):
+        """(SB, H*W, 64), the LSTM input projection of every latent texel: scene s's table is the (H*W, C) @ (C, 64)
+        product on latent[s], one library GEMM per map (the same call on the same shapes: a scene's table does not
+        depend on the scenes it shares a call with); latent.shape[0] may be SB, or scene 0's table serves all."""
         lat = phi.encoder.latent
         w = self.lstm.weight_ih
         key = (param_generation(), lat.data_ptr(), lat._version, tuple(lat.shape), w.data_ptr(), w._version)
-        if self._gate_cache is not None and self._gate_cache[0] == key:
-            return self._gate_cache[1]
-        C = lat.shape[1]
-        # (H*W, C) @ (C, 64): the LSTM input projection of every latent texel (a plain library GEMM)
-        table = torch.matmul(lat[0].detach().reshape(C, -1).t().float(), w.detach().t().float()).contiguous()
-        self._gate_cache = (key, table, lat, w)
-        return table
 
-    def _gate_tables(self, phi, SB):
-        """(SB, H*W, 64): scene s's table is _gate_table's product on latent[s] (the same call on the same
-        shapes, so a scene's table does not depend on the scenes it shares a call with); latent.shape[0] may be 1
-        (one table, repeated) or SB. Cached under _gate_table's key extended by the scene count."""
-        if SB == 1:
-            return self._gate_table(phi).unsqueeze(0)
-        lat = phi.encoder.latent
-        w = self.lstm.weight_ih
-        key = (param_generation(), lat.data_ptr(), lat._version, tuple(lat.shape), w.data_ptr(), w._version, SB)
-        if self._gates_cache is not None and self._gates_cache[0] == key:
-            return self._gates_cache[1]
-        C = lat.shape[1]
-        wt = w.detach().t().float()
-        one = [torch.matmul(lat[s].detach().reshape(C, -1).t().float(), wt) for s in range(lat.shape[0])]
-        tables = (torch.stack(one) if len(one) == SB else one[0].unsqueeze(0).repeat(SB, 1, 1)).contiguous()
-        self._gates_cache = (key, tables, lat, w)
-        return tables
+        def make():
+            wt = w.detach().t().float()
+            one = [torch.matmul(lat[s].detach().reshape(lat.shape[1], -1).t().float(), wt)
+                   for s in range(SB if lat.shape[0] == SB else 1)]
+            if SB == 1:
+                return one[0].unsqueeze(0)
+            return (torch.stack(one) if len(one) == SB else one[0].unsqueeze(0).repeat(SB, 1, 1)).contiguous()
+        return _cached(self._gates, SB, key, make, keep=(lat, w))
 
     def cache_tensors(self):
-        """The gate tables the inference launches read (avr.graphs.GraphedRenderer keeps them alive while a
-        captured graph reads them)."""
-        return [c[1] for c in (self._gate_cache, self._gates_cache) if c is not None]
+        """The gate tables the inference launches read (avr.graphs.GraphedRenderer keeps them alive for its graph)."""
+        return [rec.value for rec in self._gates.values()]
 
     def _net_fusable(self, phi, ros):
         return (not torch.is_grad_enabled() and hasattr(phi, "can_fuse") and phi.can_fuse(ros)
@@ -473,7 +460,7 @@ class _LSTMMarch(nn.Module):
                                      lstm.weight_hh, lstm.bias_ih, lstm.bias_hh, out.weight, out.bias)
         if self.can_fuse(phi, ros):
             self.last_path = "fused"
-            world, _ = ops.raymarch(phi.fused().view(0), self._gate_table(phi), self.lstm, self.out_layer,
+            world, _ = ops.raymarch(phi.fused().view(0), self._gate_tables(phi, 1)[0], self.lstm, self.out_layer,
                                     ros[0], rds[0], init_dist[0, :, 0], self.steps)
             return world.reshape(SB, num_rays, 3)
         self.last_path = "module"
@@ -609,9 +596,6 @@ class _MarchTrain(torch.autograd.Function):
 class Raymarcher(_LSTMMarch):
     """renderers.py:290-358: LSTM march, then the coarse field at the final
     point -> (rgb, None, depth, depth)."""
-
-    def __init__(self, num_feature_channels, raymarch_steps):
-        super().__init__(num_feature_channels, raymarch_steps)
 
     def forward(self, cam2world, intrinsics, xy_pix, phi, noise=None, ray_ids=None, n_rays_total=None):
         """ray_ids (R,) / n_rays_total: as VolumeRenderer.forward (the seeded start distances are keyed by the

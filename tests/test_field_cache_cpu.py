@@ -1,9 +1,6 @@
-"""avr.field's cache bookkeeping on the CPU (no GPU, no library call): the one cache record and lookup (_Record,
-_cached), a packed blob's by-value dims per kernel precision (_Packed.dims_as), the multi-scene launches' groups
-(scene_groups) and what FusedField.cache_tensors() hands a captured graph."""
-import gc
-import weakref
-
+"""avr.field's cache bookkeeping on the CPU (no GPU, no library call; the protocol itself: tests/test_cache_cpu.py):
+a packed blob's by-value dims per kernel precision (_Packed.dims_as), the multi-scene launches' groups
+(scene_groups), what FusedField.cache_tensors() hands a captured graph, and the key of the latent map's copies."""
 import pytest
 import torch
 
@@ -12,37 +9,6 @@ from avr import _lib, field
 
 def _dims(precision=_lib.FIELD_X3):
     return _lib.FieldDims(42, 64, 64, 2, 2, 6, 1.5, precision, 0, 0, 0.0)
-
-
-class _Held:
-    """Something weakly referenceable for a record's keep field."""
-
-
-def test_cached_builds_once_per_key_and_releases_the_old_keep():
-    store, made = {}, []
-
-    def make():
-        made.append(torch.zeros(3))
-        return made[-1]
-
-    keep = _Held()
-    dead = weakref.ref(keep)
-    a = field._cached(store, "slot", ("k", 1), make, keep=keep)
-    assert field._cached(store, "slot", ("k", 1), make, keep=keep) is a and len(made) == 1
-    rec = store["slot"]
-    assert (rec.key, rec.keep) == (("k", 1), keep) and rec.value is a and rec[0] == rec.key and rec[1] is a
-    # a CPU tensor: nothing to stamp, and the join of a stampless record is a no-op
-    assert rec.stamp is None and field._stamp(a) is None
-    field._join(rec.stamp, rec.value)
-    del keep, rec
-    b = field._cached(store, "slot", ("k", 2), make, keep=_Held())
-    assert b is not a and len(made) == 2 and store["slot"].key == ("k", 2)
-    gc.collect()
-    assert dead() is None                       # the replaced entry's keep went with it
-    # another slot of the same store is its own entry; a host-side value (device=False) is never stamped
-    v = field._cached(store, "other", ("k", 2), lambda: object(), device=False)
-    assert field._cached(store, "other", ("k", 2), lambda: object(), device=False) is v
-    assert store["other"].stamp is None and store["slot"].value is b
 
 
 @pytest.mark.parametrize("packed_as", [_lib.FIELD_X3, _lib.FIELD_FP32])
@@ -88,3 +54,52 @@ def test_cache_tensors_walks_the_declared_fields():
     assert len(got) == 4 and {id(t) for t in got} == {id(blob), id(bwd), id(table), id(batch)}
     fused.invalidate()
     assert not fused._packed and fused.cache_tensors() == []
+
+
+def _latent_rebuilds(latent, change):
+    """How often FusedField._latent_cached rebuilds a copy of `latent` over: a call, a repeat, change(), a call."""
+    fused = field.FusedField(net=None)
+    made = []
+
+    def get():
+        return fused._latent_cached("copy", latent, lambda: made.append(1) or latent.detach().clone())
+    first = get()
+    assert get() is first and len(made) == 1
+    change()
+    after = get()
+    assert (after is first) == (len(made) == 1)
+    return len(made) - 1, after
+
+
+def _fused_adam_step(leaf):
+    """A step that updates the leaf's storage without advancing any version counter (torch's fused Adam)."""
+    opt = torch.optim.Adam([leaf], lr=0.1, fused=True)
+    leaf.grad = torch.ones_like(leaf)
+
+    def step():
+        versions = leaf._version
+        opt.step()
+        assert leaf._version == versions
+    return step
+
+
+def test_latent_copies_of_a_view_of_a_trainable_leaf_follow_the_optimizer():
+    """encoder.latent = param[idx] shares the leaf's storage: the optimizer-step count is in its key, as for the
+    leaf itself."""
+    leaf = torch.nn.Parameter(torch.ones(4, 16, 2, 2))
+    view = leaf[1:3]
+    assert not view.is_leaf and view._base is leaf
+    rebuilt, after = _latent_rebuilds(view, _fused_adam_step(leaf))
+    assert rebuilt == 1 and torch.equal(after, view.detach()) and not torch.equal(after, torch.ones(2, 16, 2, 2))
+    assert _latent_rebuilds(leaf, _fused_adam_step(leaf))[0] == 1
+
+
+def test_latent_copies_of_a_fixed_map_outlive_optimizer_steps_but_not_a_generation_bump():
+    plain = torch.ones(2, 16, 2, 2) * 2.0            # an encoder's output: no leaf that requires grad behind it
+    assert plain._base is None and not plain.requires_grad
+    other = torch.nn.Parameter(torch.ones(3))
+    assert _latent_rebuilds(plain, _fused_adam_step(other))[0] == 0
+    produced = (torch.nn.Parameter(torch.ones(2, 16, 2, 2)) * 2.0)   # a non-leaf with history, not a view
+    assert not produced.is_leaf and produced._base is None
+    assert _latent_rebuilds(produced, _fused_adam_step(other))[0] == 0
+    assert _latent_rebuilds(plain, field.bump_param_generation)[0] == 1

@@ -46,8 +46,8 @@ def test_march_equals_raymarch(golden, R):
     net, avr, ro, rd, init = _rays(g, R)
     with torch.no_grad():
         for steps in (0, 1, 10):
-            want, _ = ops.raymarch(net.fused().view(0), avr._gate_table(net), avr.lstm, avr.out_layer, ro, rd, init,
-                                   steps)
+            want, _ = ops.raymarch(net.fused().view(0), avr._gate_tables(net, 1)[0], avr.lstm, avr.out_layer, ro, rd,
+                                   init, steps)
             world, z = _front(net, avr, ro, rd, R, steps, 0, init_dist=init)
             assert z is None and torch.equal(world, want), (R, steps)
             assert bool(torch.isfinite(world).all())

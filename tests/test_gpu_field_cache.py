@@ -87,3 +87,47 @@ def test_lookup_features_matches_the_per_scene_launch_bit_for_bit(shared_map, mo
     got = train_common.lookup_features(fused, lat, xyz.contiguous(), SB, B)
     assert got.shape == (SB * B, 64) and torch.equal(got, ref)
     assert launches == ([] if shared_map else ["avr_latent_features_batch"])   # (per scene: through avr.ops)
+
+
+def test_a_value_cached_on_a_side_stream_inside_a_capture_is_ordered_before_its_reader():
+    """The captured adaptive step's pattern (avr.renderers: the coarse backward fills FusedField._latent_cache on
+    the graph's side stream, the band backward reads it on the capturing stream), in small: inside a capture
+    scope the side stream runs a few milliseconds of GEMMs and then fills a record; the capturing stream's hit of
+    that record must become a graph edge, so every replay copies this replay's value, not the one before."""
+    from avr.cache import _cached, capture_scope
+    n = 64 * 1024
+    src, out = torch.zeros(n, device=DEV), torch.full((n,), -1.0, device=DEV)
+    a = torch.full((2048, 2048), 1.0 / 2048, device=DEV)
+    b, c = torch.ones(2048, 2048, device=DEV), torch.empty(2048, 2048, device=DEV)
+    side = torch.cuda.Stream(device=DEV)
+    store, made = {}, []
+
+    def make():
+        made.append(1)
+        return src * 2
+
+    def delay():   # 24 x 17 GFLOP of fp32 GEMM: a few milliseconds, no allocation
+        for _ in range(12):
+            torch.mm(a, b, out=c)
+            torch.mm(a, c, out=b)
+
+    delay()        # (the GEMM library's first call, outside the capture)
+    torch.cuda.synchronize()
+    graph = torch.cuda.CUDAGraph()
+    with capture_scope(), torch.cuda.graph(graph):
+        main = torch.cuda.current_stream()
+        fork = torch.cuda.Event()
+        fork.record(main)
+        side.wait_event(fork)
+        with torch.cuda.stream(side):
+            delay()
+            value = _cached(store, "slot", "key", make)
+        assert _cached(store, "slot", "key", make) is value and made == [1]   # a hit, on the capturing stream
+        out.copy_(value)
+        main.wait_stream(side)
+    for fill in (1.0, 2.0, 3.0):
+        src.fill_(fill)
+        graph.replay()
+        torch.cuda.synchronize()
+        assert bool((out == 2 * fill).all()), (fill, out[:4].tolist())
+    assert made == [1] and bool((b == 1).all())
