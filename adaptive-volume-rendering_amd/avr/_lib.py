@@ -256,8 +256,19 @@ def stream_of(t):
     return c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
 
 
-def ptr(t):
-    return None if t is None else c_void_p(t.data_ptr())
+def size_query(name, *args, n=1):
+    """The size a `*_bytes` / `*_floats` / `*_sizes` entry reports through its trailing int64 out-arguments: an
+    int, or with n > 1 a tuple of n."""
+    out = [i64(0) for _ in range(n)]
+    call(name, *args, *[ctypes.byref(o) for o in out])
+    return out[0].value if n == 1 else tuple(o.value for o in out)
+
+
+def ptr(t, offset=0):
+    """t's device address, `offset` elements of t in (None for no tensor)."""
+    if t is None:
+        return None
+    return c_void_p(t.data_ptr() + offset * t.element_size() if offset else t.data_ptr())
 
 
 def require_device(*tensors):

@@ -75,7 +75,7 @@ OPS = ("world_rays", "rays_sample_coarse", "composite_depth", "depth_from_world_
        "weight_grads", "weight_grads_specs", "latent_features")
 FIELD_METHODS = ("forward_rays", "forward_rays_batch", "forward_points_multiview", "forward_points", "forward_train")
 FUNCTIONS = (("ops", "_Depth"), ("ops", "_Composite"), ("ops", "_DepthOfPoints"), ("field", "_FieldTrain"),
-             ("bn_train", "_FieldTrainBN"), ("renderers", "_MarchTrain"),
+             ("bn_train", "_FieldTrainBN"), ("layer_train", "_FieldTrainLayers"), ("renderers", "_MarchTrain"),
              ("renderers", "_Band"))
 
 
@@ -84,8 +84,8 @@ def install():
     global _installed
     if _installed:
         return
-    from . import bn_train, field, ops, renderers
-    mods = {"ops": ops, "field": field, "bn_train": bn_train, "renderers": renderers}
+    from . import bn_train, field, layer_train, ops, renderers
+    mods = {"ops": ops, "field": field, "bn_train": bn_train, "layer_train": layer_train, "renderers": renderers}
     for n in OPS:
         f = getattr(ops, n)
         if not getattr(f, "__avr_checked__", False):

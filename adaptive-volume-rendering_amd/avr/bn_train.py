@@ -21,11 +21,10 @@ import ctypes
 
 import torch
 
-from . import _lib, ops
-from ._lib import BnLayer, call, ptr, stream_of
+from . import _lib, ops, train_common as tc
+from ._lib import call, ptr, stream_of
 from .field import fused_eligible, softplus_beta, train_param_names, uses_bn
-from .train_common import (forward_train, input_grads, lin_z_epilogue, lookup_features,
-                           padded_z_features)
+from .train_common import forward_train, lin_z_epilogue, lookup_features, padded_z_features
 
 F32 = torch.float32
 
@@ -69,25 +68,6 @@ class _Stats:
     def __init__(self, H, dev):
         buf = torch.empty(3, H, device=dev, dtype=F32)
         self.mu, self.invstd, self.scale = buf[0], buf[1], buf[2]
-
-
-def _layer(**kw):
-    """An avr_bn_layer from keyword fields (tensors become their device addresses)."""
-    l = BnLayer()
-    for k, v in kw.items():
-        setattr(l, k, v.data_ptr() if isinstance(v, torch.Tensor) else v)
-    return l
-
-
-def _run(dims, layer, stream):
-    call("avr_bn_layer_run", ctypes.byref(dims), ctypes.byref(layer), stream)
-
-
-def _partial(M, H, dev):
-    """The per-workgroup column partials of avr_bn_layer_run plus the fold scratch of avr_bn_stats."""
-    n = ctypes.c_int64(0)
-    call("avr_bn_partial_floats", M, H, ctypes.byref(n))
-    return torch.empty(n.value, device=dev, dtype=F32)
 
 
 def _momentum(bn):
@@ -165,27 +145,26 @@ class _FieldTrainBN(torch.autograd.Function):
             # max |relu(bn_0(.))| of each hidden GEMM's operand (the operands themselves are not stored: the
             # backward's relu masks and the weight gradients rebuild them from X / N and the statistics)
             amax = torch.zeros(2 * nb + 2, device=dev, dtype=torch.int32)
-            part = _partial(M, H, dev)
+            part = tc.layer_partial(M, H, dev)
             st1 = [_Stats(H, dev) for _ in range(nb)]
             st2 = [_Stats(H, dev) for _ in range(nb)]
             bns = _bn_blocks(mlp)
-            blob = entry.packed
-            _run(dims, _layer(n_rows=M, mode=_lib.BN_FWD, prologue=_lib.BN_PLAIN, in_dim=64, in_valid=d_in,
-                              src=zfp, ld_src=zs, blob=blob, layer=0, bias=b_in, out=X[0], partial=part,
-                              **lin_z(0)), stream)
+
+            def run(**kw):   # one forward layer GEMM over the M rows
+                tc.run_layer(dims, tc.bn_layer(n_rows=M, mode=_lib.BN_FWD, blob=entry.packed, partial=part, **kw),
+                             stream)
+            run(prologue=_lib.BN_PLAIN, in_dim=64, in_valid=d_in, src=zfp, ld_src=zs, layer=0, bias=b_in, out=X[0],
+                **lin_z(0))
             for b in range(nb):
                 bn = bns[b]
                 _bn_stats(bn, part, M, H, st1[b], stream)
-                _run(dims, _layer(n_rows=M, mode=_lib.BN_FWD, prologue=_lib.BN_RELU, in_dim=H, in_valid=H,
-                                  src=X[b], ld_src=H, in_mu=st1[b].mu, in_scale=st1[b].scale, in_shift=betas[b],
-                                  operand_max=amax[2 * b:], blob=blob, layer=2 + 2 * b,
-                                  bias=b0[b], out=N[b], partial=part), stream)
+                run(prologue=_lib.BN_RELU, in_dim=H, in_valid=H, src=X[b], ld_src=H, in_mu=st1[b].mu,
+                    in_scale=st1[b].scale, in_shift=betas[b], operand_max=amax[2 * b:], layer=2 + 2 * b, bias=b0[b],
+                    out=N[b])
                 _bn_stats(bn, part, M, H, st2[b], stream)
-                _run(dims, _layer(n_rows=M, mode=_lib.BN_FWD, prologue=_lib.BN_RELU, in_dim=H, in_valid=H,
-                                  src=N[b], ld_src=H, in_mu=st2[b].mu, in_scale=st2[b].scale, in_shift=betas[b],
-                                  operand_max=amax[2 * b + 1:], blob=blob,
-                                  layer=3 + 2 * b, bias=b1[b], add1=X[b], out=X[b + 1], partial=part,
-                                  **lin_z(b + 1)), stream)
+                run(prologue=_lib.BN_RELU, in_dim=H, in_valid=H, src=N[b], ld_src=H, in_mu=st2[b].mu,
+                    in_scale=st2[b].scale, in_shift=betas[b], operand_max=amax[2 * b + 1:], layer=3 + 2 * b,
+                    bias=b1[b], add1=X[b], out=X[b + 1], **lin_z(b + 1))
             # lin_out on relu(x) (4 outputs; models.py:592), sigmoid rgb / relu sigma (models.py:856-862), and
             # max relu(x) for its weight gradient's scale (relu(x) itself is not stored)
             out, a_max = ops.lin_out_rows(X[nb], P["lin_out.weight"].detach(), P["lin_out.bias"].detach())
@@ -228,12 +207,16 @@ class _FieldTrainBN(torch.autograd.Function):
             dn_max = torch.zeros(max(nb, 1), device=dev, dtype=torch.int32)
             gp2 = torch.empty(M, H, device=dev, dtype=F32)
             gp1 = torch.empty(max(nb, 1), M, H, device=dev, dtype=F32)
-            part = _partial(M, H, dev)
+            part = tc.layer_partial(M, H, dev)
             dgam = torch.zeros(nb, H, device=dev, dtype=F32)
             dbet = torch.zeros(nb, H, device=dev, dtype=F32)
             gs1 = [torch.empty(3, H, device=dev, dtype=F32) for _ in range(nb)]   # coef, m1, m2 of point 1
             gs2 = torch.empty(3, H, device=dev, dtype=F32)
             gammas = [bns[b].weight.detach().to(F32).contiguous() for b in range(nb)]
+
+            def run(**kw):   # one transposed layer GEMM over the M rows
+                tc.run_layer(dims, tc.bn_layer(n_rows=M, mode=_lib.BN_BWD, in_dim=H, in_valid=H, blob=bwd,
+                                               partial=part, **kw), stream)
             for b in range(nb - 1, -1, -1):
                 # fc_1[b]^T: operand = Gx[b+1] (for b < nb-1 built in the prologue from block b+1's BN backward)
                 if b == nb - 1:
@@ -243,18 +226,15 @@ class _FieldTrainBN(torch.autograd.Function):
                     pro = dict(prologue=_lib.BN_GRAD, src=gp1[b + 1], ld_src=H, src_pre=X[b + 1], src_res=Gx[b + 2],
                                in_mu=st1[b + 1].mu, in_invstd=st1[b + 1].invstd, in_scale=c[0], in_m1=c[1],
                                in_m2=c[2], operand_out=Gx[b + 1], operand_max=gmax[b + 1:])
-                _run(dims, _layer(n_rows=M, mode=_lib.BN_BWD, in_dim=H, in_valid=H, blob=bwd, layer=3 + 2 * b,
-                                  out=gp2, pre_rows=N[b], out_mu=st2[b].mu, out_invstd=st2[b].invstd,
-                                  out_scale=st2[b].scale, out_shift=betas[b], partial=part, **pro), stream)
+                run(layer=3 + 2 * b, out=gp2, pre_rows=N[b], out_mu=st2[b].mu, out_invstd=st2[b].invstd,
+                    out_scale=st2[b].scale, out_shift=betas[b], **pro)
                 call("avr_bn_grad_stats", ptr(part), M, H, ptr(gammas[b]), ptr(st2[b].invstd), ptr(gs2[0]),
                      ptr(gs2[1]), ptr(gs2[2]), ptr(dgam[b]), ptr(dbet[b]), stream)
                 # fc_0[b]^T: operand = d loss / d fc_0 output = BN backward of gp2 (stored as DN[b])
-                _run(dims, _layer(n_rows=M, mode=_lib.BN_BWD, prologue=_lib.BN_GRAD, in_dim=H, in_valid=H,
-                                  src=gp2, ld_src=H, src_pre=N[b], in_mu=st2[b].mu, in_invstd=st2[b].invstd,
-                                  in_scale=gs2[0], in_m1=gs2[1], in_m2=gs2[2], operand_out=DN[b],
-                                  operand_max=dn_max[b:], blob=bwd, layer=2 + 2 * b, out=gp1[b], pre_rows=X[b],
-                                  out_mu=st1[b].mu, out_invstd=st1[b].invstd, out_scale=st1[b].scale,
-                                  out_shift=betas[b], partial=part), stream)
+                run(prologue=_lib.BN_GRAD, src=gp2, ld_src=H, src_pre=N[b], in_mu=st2[b].mu, in_invstd=st2[b].invstd,
+                    in_scale=gs2[0], in_m1=gs2[1], in_m2=gs2[2], operand_out=DN[b], operand_max=dn_max[b:],
+                    layer=2 + 2 * b, out=gp1[b], pre_rows=X[b], out_mu=st1[b].mu, out_invstd=st1[b].invstd,
+                    out_scale=st1[b].scale, out_shift=betas[b])
                 c = gs1[b]
                 call("avr_bn_grad_stats", ptr(part), M, H, ptr(gammas[b]), ptr(st1[b].invstd), ptr(c[0]), ptr(c[1]),
                      ptr(c[2]), ptr(dgam[b]), ptr(dbet[b]), stream)
@@ -270,31 +250,21 @@ class _FieldTrainBN(torch.autograd.Function):
             lat_max = fused.latent_max_bits(latent)
             layers = []
             for b in range(nb):
-                layers.append((DN[b], X[b], dn_max[b:b + 1], amax[2 * b:2 * b + 1], True,
-                               (st1[b].mu, st1[b].scale, betas[b])))
-                layers.append((Gx[b + 1], N[b], gmax[b + 1:b + 2], amax[2 * b + 1:2 * b + 2], True,
-                               (st2[b].mu, st2[b].scale, betas[b])))
+                layers.append((f"blocks.{b}.fc_0", (DN[b], X[b], dn_max[b:b + 1], amax[2 * b:2 * b + 1], True,
+                                                    (st1[b].mu, st1[b].scale, betas[b]))))
+                layers.append((f"blocks.{b}.fc_1", (Gx[b + 1], N[b], gmax[b + 1:b + 2], amax[2 * b + 1:2 * b + 2], True,
+                                                    (st2[b].mu, st2[b].scale, betas[b]))))
             for b in range(nz):
-                layers.append((Gx[b], lat_feat, gmax[b:b + 1], lat_max, True))
+                layers.append((f"lin_z.{b}", (Gx[b], lat_feat, gmax[b:b + 1], lat_max, True)))
             zf_max = ops._max_bits(zfp)
-            layers.append((Gx[0], zfp, gmax[0:1], zf_max, True))
-            layers.append((d4, X[nb], d4_max, a_max, True, "relu"))   # relu(X[nb]) rebuilt in the staging
-            res = ops.weight_grads(layers, M)
-            grads = {"lin_out.weight": res[-1][0], "lin_out.bias": res[-1][1]}
-            w_in, b_in = res[-2]
-            grads["lin_in.weight"], grads["lin_in.bias"] = w_in[:, :net.d_in].contiguous(), b_in
+            layers.append(("lin_in", (Gx[0], zfp, gmax[0:1], zf_max, True)))
+            layers.append(("lin_out", (d4, X[nb], d4_max, a_max, True, "relu")))   # relu(X[nb]) rebuilt in the staging
+            grads = tc.named_weight_grads(layers, M, net.d_in)
             for b in range(nb):
-                grads[f"blocks.{b}.fc_0.weight"], grads[f"blocks.{b}.fc_0.bias"] = res[2 * b]
-                grads[f"blocks.{b}.fc_1.weight"], grads[f"blocks.{b}.fc_1.bias"] = res[2 * b + 1]
-                grads[f"blocks.{b}.bn_0.weight"] = dgam[b]
-                grads[f"blocks.{b}.bn_0.bias"] = dbet[b]
-            for b in range(nz):
-                grads[f"lin_z.{b}.weight"], grads[f"lin_z.{b}.bias"] = res[2 * nb + b]
-        g_feat = g_zf = None
+                grads[f"blocks.{b}.bn_0.weight"], grads[f"blocks.{b}.bn_0.bias"] = dgam[b], dbet[b]
+        g_feat = None
         if (want_latent or want_xyz) and nz > 0 and not net.stop_encoder_grad:   # a detached lookup carries none
             g_feat = ops.sum_of_products([(Gx[b], P[f"lin_z.{b}.weight"].detach()) for b in range(nz)])
-        if want_xyz:
-            g_zf = Gx[0] @ P["lin_in.weight"].detach()
-        d_latent, d_xyz = input_grads(fused, xyz, viewdirs, latent, want_latent, want_xyz, g_feat, g_zf)
-        return (None, None, None, d_xyz, None, d_latent) + tuple(
-            grads[n] if ctx.needs_input_grad[6 + i] else None for i, n in enumerate(names))
+        d_latent, d_xyz = tc.mlp_input_grads(fused, xyz, viewdirs, latent, want_latent, want_xyz, g_feat, Gx[0],
+                                             P["lin_in.weight"])
+        return tc.backward_result(ctx.needs_input_grad, names, grads, d_xyz, d_latent)

@@ -22,10 +22,11 @@ import weakref
 import torch
 
 from . import _lib, ops, train_common
-from ._lib import FieldDims, ResnetFCWeights, ViewDesc, call, ptr, require_device, scene_groups, stream_of
+from ._lib import (FieldDims, ResnetFCWeights, ViewDesc, call, ptr, require_device, scene_groups, size_query,
+                   stream_of)
 from .cache import (_EXPLICIT_GEN, _MODULE_GEN, _PARAM_GEN, _Record, _cached, _hit, _slot_current, _stamp, _version_key,
                     bump_param_generation, param_generation)   # noqa: F401 (the last two: this module's API too)
-from .train_common import input_grads, latent_grad_hip, latent_grad_on_hip, lookup_features
+from .train_common import feat_grad as _feat_grad, latent_grad_hip, latent_grad_on_hip, lookup_features
 
 F32 = torch.float32
 _blob = operator.attrgetter("packed")   # the device tensor of a _Packed: what its record's stamp marks
@@ -281,8 +282,7 @@ class FusedField:
     def _pack_weights(self, mlp, dims):
         """avr_field_pack's arguments for mlp: (blob floats, weight pointers, the tensors behind them, whether every
         pointer is a parameter or buffer read in place)."""
-        n = ctypes.c_int64(0)
-        _lib.check(_lib.load().avr_field_packed_floats(ctypes.byref(dims), ctypes.byref(n)), "avr_field_packed_floats")
+        n = size_query("avr_field_packed_floats", ctypes.byref(dims))
         w = ResnetFCWeights()
         keep = []
         derived = [False]
@@ -315,7 +315,7 @@ class FusedField:
             if dims.spade:   # scale_z[b](z) * x + lin_z[b](z) (models.py:585-587): both as per-texel tables
                 w.scale_z_w[b], w.scale_z_b[b] = P(mlp.scale_z[b].weight), P(mlp.scale_z[b].bias)
         require_device(*keep)
-        return n.value, w, keep, not (dims.bn or derived[0])
+        return n, w, keep, not (dims.bn or derived[0])
 
     def packed_bwd(self, coarse, entry=None):
         """Transposed fc_0 / fc_1 fragments for the backward kernel, cached with
@@ -323,10 +323,8 @@ class FusedField:
         entry = entry or self.packed(coarse)
         if not _hit(entry.bwd, None):
             dims = entry.dims_as(_lib.FIELD_X3)   # (the backward blob is x3 fragments; the C side reads no precision)
-            n = ctypes.c_int64(0)
-            _lib.check(_lib.load().avr_field_bwd_packed_floats(ctypes.byref(dims), ctypes.byref(n)),
-                       "avr_field_bwd_packed_floats")
-            bwd = torch.empty(n.value, device=entry.packed.device, dtype=F32)
+            n = size_query("avr_field_bwd_packed_floats", ctypes.byref(dims))
+            bwd = torch.empty(n, device=entry.packed.device, dtype=F32)
             call("avr_field_pack_bwd", ctypes.byref(dims), ctypes.byref(entry.weights), ptr(bwd), stream_of(bwd))
             entry.bwd = _Record(None, bwd, None, _stamp(bwd))
         return entry.bwd.value
@@ -518,30 +516,6 @@ class FusedField:
         return train_common.forward_train(self, xyz, viewdirs, coarse, _FieldTrain, train_param_names)
 
 
-def _feat_grad(fused, entry, bwd, Gz, P, Mt):
-    """The looked-up latent features' gradient sum_b Gz[b] . W_z[b] (the point / latent gradients' input):
-    avr_bn_layer_run's lin_z[b]^T layers from the backward blob (x3, ABI 14), one launch per layer adding the
-    previous layers' sum in its epilogue, where they apply (d_latent == d_hidden, ReLU, 64..512 wide); else
-    fp32 library GEMMs (avr.ops.sum_of_products). entry: anything holding the blob's dims (an x3 copy is made)."""
-    from .bn_train import _layer, _partial, _run   # (avr.bn_train imports this module)
-    dims = entry.dims.with_precision(_lib.FIELD_X3)
-    H, nz = dims.d_hidden, dims.n_lin_z
-    if not (dims.d_latent == H and H in (64, 128, 256, 512) and not dims.spade and not dims.bn
-            and not dims.beta > 0 and Mt > 0 and all(g.is_contiguous() for g in Gz)):
-        return ops.sum_of_products([(Gz[b], P[f"lin_z.{b}.weight"].detach()) for b in range(nz)])
-    dev = Gz[0].device
-    part = _partial(Mt, H, dev)
-    stream = stream_of(Gz[0])
-    prev = None
-    for b in range(nz):
-        out = torch.empty(Mt, H, device=dev, dtype=F32)
-        _run(dims, _layer(n_rows=Mt, mode=_lib.BN_BWD, prologue=_lib.BN_PLAIN, in_dim=H, in_valid=H, src=Gz[b],
-                          ld_src=H, blob=bwd, layer=_lib.BN_LAYER_LIN_Z_T + b, add1=prev, out=out, partial=part),
-             stream)
-        prev = out
-    return prev
-
-
 def train_param_names(mlp):
     """The ResnetFC parameters the training path differentiates, in a fixed order."""
     names = ["lin_in.weight", "lin_in.bias", "lin_out.weight", "lin_out.bias"]
@@ -560,8 +534,8 @@ def _bwd_chain(dims, entry, bwd, masks, B, Mt, out, grad_out, act):
     g_max = torch.zeros(n_l, device=out.device, dtype=torch.int32)
     for g0, n, mask in masks:
         call("avr_field_bwd", ctypes.byref(dims), ptr(entry.packed), ptr(bwd), n, B, ptr(out[g0]),
-             ptr(grad_out[g0]), ptr(mask), ctypes.c_void_p(act.data_ptr() + g0 * B * H * 4), Mt,
-             ctypes.c_void_p(G.data_ptr() + g0 * B * H * 4), Mt, ptr(g_max), stream_of(G))
+             ptr(grad_out[g0]), ptr(mask), ptr(act, g0 * B * H), Mt, ptr(G, g0 * B * H), Mt, ptr(g_max),
+             stream_of(G))
     return G, g_max
 
 
@@ -573,28 +547,21 @@ def _weight_grads(dims, Mt, G, g_max, act, act_max, lat_feat, lat_max, zf, d4, d
     (d4, the last block's output) -- no per-layer views or checks."""
     H, nb, nz, d_latent = dims.d_hidden, dims.n_blocks, dims.n_lin_z, dims.d_latent
     Gp, Ap, gmp, amp, lay = G.data_ptr(), act.data_ptr(), g_max.data_ptr(), act_max.data_ptr(), Mt * H * 4
-    specs = [(Gp + k * lay, H, Ap + k * lay, H, H, H, gmp + 4 * k, amp + 4 * k, True, None, None, None, 0)
-             for k in range(2 * nb)]
+    layers = [(f"blocks.{k // 2}.fc_{k % 2}",
+               (Gp + k * lay, H, Ap + k * lay, H, H, H, gmp + 4 * k, amp + 4 * k, True, None, None, None, 0))
+              for k in range(2 * nb)]
     for b in range(nz):
         k = 2 * b - 1 if b > 0 else 2 * nb
-        specs.append((Gp + k * lay, H, lat_feat.data_ptr(), d_latent, H, d_latent, gmp + 4 * k,
-                      lat_max.data_ptr(), False, None, None, None, 0))
-    specs.append((Gp + 2 * nb * lay, H, zf.data_ptr(), zf.shape[1], H, zf.shape[1], gmp + 8 * nb,
-                  amp + 4 * (2 * nb + 1), True, None, None, None, 0))
-    specs.append((d4.data_ptr(), 4, Ap + 2 * nb * lay, H, 4, H, d4_max.data_ptr(), amp + 8 * nb, True, None, None,
-                  None, 0))
-    res = ops.weight_grads_specs(specs, Mt, G.device, stream_of(G))
-    grads = {"lin_out.weight": res[-1][0], "lin_out.bias": res[-1][1]}
-    res = res[:-1]
-    for b in range(nb):
-        grads[f"blocks.{b}.fc_0.weight"], grads[f"blocks.{b}.fc_0.bias"] = res[2 * b]
-        grads[f"blocks.{b}.fc_1.weight"], grads[f"blocks.{b}.fc_1.bias"] = res[2 * b + 1]
+        layers.append((f"lin_z.{b}", (Gp + k * lay, H, lat_feat.data_ptr(), d_latent, H, d_latent, gmp + 4 * k,
+                                      lat_max.data_ptr(), False, None, None, None, 0)))
+    layers.append(("lin_in", (Gp + 2 * nb * lay, H, zf.data_ptr(), zf.shape[1], H, zf.shape[1], gmp + 8 * nb,
+                              amp + 4 * (2 * nb + 1), True, None, None, None, 0)))
+    layers.append(("lin_out", (d4.data_ptr(), 4, Ap + 2 * nb * lay, H, 4, H, d4_max.data_ptr(), amp + 8 * nb, True,
+                               None, None, None, 0)))
+    grads = train_common.named_weight_grads(layers, Mt, dims.d_in, specs_on=(G.device, stream_of(G)))
     for b in range(nz):
-        grads[f"lin_z.{b}.weight"] = res[2 * nb + b][0]
-        # lin_z[b]'s output gradient is the gradient at block b's input
-        grads[f"lin_z.{b}.bias"] = res[2 * b - 1][1] if b > 0 else res[-1][1]
-    w_in, b_in = res[-1]
-    grads["lin_in.weight"], grads["lin_in.bias"] = w_in[:, :dims.d_in].contiguous(), b_in
+        # lin_z[b]'s output gradient is the gradient at block b's input: the bias gradient of the layer writing it
+        grads[f"lin_z.{b}.bias"] = grads[f"blocks.{b - 1}.fc_1.bias"] if b > 0 else grads["lin_in.bias"]
     return grads
 
 
@@ -693,15 +660,12 @@ class _FieldTrain(torch.autograd.Function):
         tables = fused.tables_batch(coarse, SB, fast=True, entry=entry)
         masks = []
         for g0, n in scene_groups(SB):     # one launch per group of scenes
-            act_n, mask_n = ctypes.c_int64(0), ctypes.c_int64(0)
-            _lib.check(_lib.load().avr_field_train_sizes(ctypes.byref(dims), n, B, ctypes.byref(act_n),
-                                                         ctypes.byref(mask_n)), "avr_field_train_sizes")
+            _, mask_n = size_query("avr_field_train_sizes", ctypes.byref(dims), n, B, n=2)
             views = fused.views(range(g0, g0 + n))
-            mask = torch.empty(max(mask_n.value, 1), device=dev, dtype=torch.int32)
+            mask = torch.empty(max(mask_n, 1), device=dev, dtype=torch.int32)
             call("avr_field_fwd_points_train", ctypes.byref(dims), views, n, ptr(entry.packed), ptr(tables[g0]),
-                 ptr(p[g0]), ptr(v[g0]), B, ptr(out[g0]), ctypes.c_void_p(act.data_ptr() + g0 * B * H * 4), Mt,
-                 ptr(mask), ptr(act_max), ctypes.c_void_p(zf.data_ptr() + g0 * B * zs * 4), zs,
-                 ctypes.c_void_p(act_max.data_ptr() + 4 * n_l), stream_of(p))
+                 ptr(p[g0]), ptr(v[g0]), B, ptr(out[g0]), ptr(act, g0 * B * H), Mt, ptr(mask), ptr(act_max),
+                 ptr(zf, g0 * B * zs), zs, ptr(act_max, n_l), stream_of(p))
             masks.append((g0, n, mask))
         ctx.fused, ctx.coarse, ctx.names, ctx.entry = fused, coarse, names, entry
         ctx.act, ctx.act_max, ctx.masks, ctx.zf = act, act_max, masks, zf
@@ -751,7 +715,6 @@ class _FieldTrain(torch.autograd.Function):
             d_xyz = _point_grad_hip(fused, entry, bwd, ctx.tables, xyz, viewdirs, latent, p, G[2 * nb], Gz, P)
         elif want_latent or want_xyz:
             g_feat = _feat_grad(fused, entry, bwd, Gz, P, Mt) if nz > 0 else None
-            g_zf = G[2 * nb] @ P["lin_in.weight"].detach() if want_xyz else None
-            d_latent, d_xyz = input_grads(fused, xyz, viewdirs, latent, want_latent, want_xyz, g_feat, g_zf)
-        return (None, None, None, d_xyz, None, d_latent) + tuple(
-            grads[n] if ctx.needs_input_grad[6 + i] else None for i, n in enumerate(names))
+            d_latent, d_xyz = train_common.mlp_input_grads(fused, xyz, viewdirs, latent, want_latent, want_xyz, g_feat,
+                                                           G[2 * nb], P["lin_in.weight"])
+        return train_common.backward_result(ctx.needs_input_grad, names, grads, d_xyz, d_latent)

@@ -23,12 +23,11 @@ statistics: the operand is relu(x), the backward's mask [pre > 0]) with the elem
 """
 import torch
 
-from . import _lib, ops
+from . import _lib, ops, train_common as tc
 from ._lib import stream_of
-from .field import _feat_grad, fused_eligible, softplus_beta, train_param_names, uses_bn
+from .field import fused_eligible, softplus_beta, train_param_names, uses_bn
 from .models import combine_interleaved
-from .train_common import (forward_train, gather_rows as _gather, input_grads, lin_z_epilogue,
-                           padded_z_features)
+from .train_common import forward_train, gather_rows as _gather, lin_z_epilogue, padded_z_features
 
 F32 = torch.float32
 
@@ -70,6 +69,17 @@ class _Ident:
     def __init__(self, H, dev):
         self.zero = torch.zeros(H, device=dev, dtype=F32)
         self.one = torch.ones(H, device=dev, dtype=F32)
+        hidden = dict(in_dim=H, in_valid=H, ld_src=H)
+        self._fields = {
+            _lib.BN_FWD: dict(hidden, mode=_lib.BN_FWD, prologue=_lib.BN_RELU, in_mu=self.zero, in_scale=self.one,
+                              in_shift=self.zero),
+            _lib.BN_BWD: dict(hidden, mode=_lib.BN_BWD, prologue=_lib.BN_PLAIN, out_mu=self.zero, out_invstd=self.one,
+                              out_scale=self.one, out_shift=self.zero)}
+
+    def layer(self, mode, **kw):
+        """The avr_bn_layer of a hidden (d_hidden x d_hidden) layer under these statistics: forward on the operand
+        relu(src), backward W^T . src masked by [pre_rows > 0]; kw names what differs between the calls."""
+        return tc.bn_layer(**self._fields[mode], **kw)
 
 
 class _FieldTrainLayers(torch.autograd.Function):
@@ -78,7 +88,6 @@ class _FieldTrainLayers(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, fused, coarse, names, xyz, viewdirs, latent, *params):
-        from .bn_train import _layer, _partial, _run   # (per call: scripts/layer_train_debug.py wraps them there)
         net = fused.net
         mlp = fused._mlp(coarse)
         P = dict(zip(names, params))
@@ -111,14 +120,14 @@ class _FieldTrainLayers(torch.autograd.Function):
             b0 = [P[f"blocks.{b}.fc_0.bias"].detach().to(F32).contiguous() for b in range(nb)]
             b1 = [(P[f"blocks.{b}.fc_1.bias"].detach().to(F32) + fold(b + 1)).contiguous() for b in range(nb)]
             idt = _Ident(H, dev)
-            part = _partial(M1, H, dev)
+            part = tc.layer_partial(M1, H, dev)
             amax = torch.zeros(2 * nb, device=dev, dtype=torch.int32)
             blob = entry.packed
             rows = lambda b: M1 if b < cl else M2   # noqa: E731  (rows of block b)
             Xpre = [torch.empty(M1, H, device=dev, dtype=F32)]
-            _run(dims, _layer(n_rows=M1, mode=_lib.BN_FWD, prologue=_lib.BN_PLAIN, in_dim=64, in_valid=d_in, src=zfp,
-                              ld_src=zs, blob=blob, layer=0, bias=b_in, out=Xpre[0], partial=part, **lin_z(0)),
-                 stream)
+            tc.run_layer(dims, tc.bn_layer(n_rows=M1, mode=_lib.BN_FWD, prologue=_lib.BN_PLAIN, in_dim=64,
+                                           in_valid=d_in, src=zfp, ld_src=zs, blob=blob, layer=0, bias=b_in,
+                                           out=Xpre[0], partial=part, **lin_z(0)), stream)
             Xin, N = [], []
             for b in range(nb):
                 x = Xpre[b]
@@ -130,15 +139,12 @@ class _FieldTrainLayers(torch.autograd.Function):
                 Xin.append(x)
                 m = rows(b)
                 N.append(torch.empty(m, H, device=dev, dtype=F32))
-                _run(dims, _layer(n_rows=m, mode=_lib.BN_FWD, prologue=_lib.BN_RELU, in_dim=H, in_valid=H, src=x,
-                                  ld_src=H, in_mu=idt.zero, in_scale=idt.one, in_shift=idt.zero,
-                                  operand_max=amax[2 * b:], blob=blob, layer=2 + 2 * b, bias=b0[b], out=N[b],
-                                  partial=part), stream)
+                tc.run_layer(dims, idt.layer(_lib.BN_FWD, n_rows=m, src=x, operand_max=amax[2 * b:], blob=blob,
+                                             layer=2 + 2 * b, bias=b0[b], out=N[b], partial=part), stream)
                 Xpre.append(torch.empty(m, H, device=dev, dtype=F32))
-                _run(dims, _layer(n_rows=m, mode=_lib.BN_FWD, prologue=_lib.BN_RELU, in_dim=H, in_valid=H, src=N[b],
-                                  ld_src=H, in_mu=idt.zero, in_scale=idt.one, in_shift=idt.zero,
-                                  operand_max=amax[2 * b + 1:], blob=blob, layer=3 + 2 * b, bias=b1[b], add1=x,
-                                  out=Xpre[b + 1], partial=part, **lin_z(b + 1)), stream)
+                tc.run_layer(dims, idt.layer(_lib.BN_FWD, n_rows=m, src=N[b], operand_max=amax[2 * b + 1:], blob=blob,
+                                             layer=3 + 2 * b, bias=b1[b], add1=x, out=Xpre[b + 1], partial=part,
+                                             **lin_z(b + 1)), stream)
             # lin_out + sigmoid / relu in one pass (max relu(x) for its weight gradient; relu(x) not stored)
             out, a_max = ops.lin_out_rows(Xpre[nb], P["lin_out.weight"].detach(), P["lin_out.bias"].detach())
             out = out.reshape(SB, B, 4)
@@ -149,7 +155,6 @@ class _FieldTrainLayers(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, grad_out):
-        from .bn_train import _layer, _partial, _run
         xyz, viewdirs, latent, out, *params = ctx.saved_tensors
         Xpre, Xin, N, S, amax, zfp, a_max, idt, p, cl = ctx.keep
         ctx.keep = None
@@ -170,7 +175,7 @@ class _FieldTrainLayers(torch.autograd.Function):
         want_xyz = ctx.needs_input_grad[3]
         with torch.no_grad():
             bwd = fused.packed_bwd(ctx.coarse, entry)
-            part = _partial(M1, H, dev)
+            part = tc.layer_partial(M1, H, dev)
             # the activations' backward (d4), lin_out^T and its relu's backward in one pass
             d4, g, d4_max = ops.lin_out_rows_bwd(grad_out.reshape(M2, 4), out.reshape(M2, 4),
                                                  P["lin_out.weight"].detach(), Xpre[nb])
@@ -190,18 +195,16 @@ class _FieldTrainLayers(torch.autograd.Function):
                 m = M1 if b < cl else M2
                 # fc_1^T: gradient at N[b]; fc_0^T: the fc_0 path's gradient at X'[b]
                 gp2 = torch.empty(m, H, device=dev, dtype=F32)
-                _run(dims, _layer(n_rows=m, mode=_lib.BN_BWD, prologue=_lib.BN_PLAIN, in_dim=H, in_valid=H, src=g,
-                                  ld_src=H, operand_max=omax[2 * b + 1:], blob=bwd, layer=3 + 2 * b, out=gp2,
-                                  pre_rows=N[b], out_mu=idt.zero, out_invstd=idt.one, out_scale=idt.one,
-                                  out_shift=idt.zero, partial=part), stream)
+                tc.run_layer(dims, idt.layer(_lib.BN_BWD, n_rows=m, src=g, operand_max=omax[2 * b + 1:], blob=bwd,
+                                             layer=3 + 2 * b, out=gp2, pre_rows=N[b], partial=part), stream)
                 # fc_0^T, the residual's g added in its epilogue: d loss / d X'[b] (residual + fc_0 path)
                 gin = torch.empty(m, H, device=dev, dtype=F32)
-                _run(dims, _layer(n_rows=m, mode=_lib.BN_BWD, prologue=_lib.BN_PLAIN, in_dim=H, in_valid=H, src=gp2,
-                                  ld_src=H, operand_max=omax[2 * b:], blob=bwd, layer=2 + 2 * b, out=gin,
-                                  pre_rows=Xin[b], out_mu=idt.zero, out_invstd=idt.one, out_scale=idt.one,
-                                  out_shift=idt.zero, add1=g, out_max=fc0t_max[b:b + 1], partial=part), stream)
-                blk[b] = [(gp2, Xin[b], omax[2 * b:2 * b + 1], amax[2 * b:2 * b + 1], True, relu_x),
-                          (g, N[b], omax[2 * b + 1:2 * b + 2], amax[2 * b + 1:2 * b + 2], True, relu_x)]
+                tc.run_layer(dims, idt.layer(_lib.BN_BWD, n_rows=m, src=gp2, operand_max=omax[2 * b:], blob=bwd,
+                                             layer=2 + 2 * b, out=gin, pre_rows=Xin[b], add1=g,
+                                             out_max=fc0t_max[b:b + 1], partial=part), stream)
+                blk[b] = [
+                    (f"blocks.{b}.fc_0", (gp2, Xin[b], omax[2 * b:2 * b + 1], amax[2 * b:2 * b + 1], True, relu_x)),
+                    (f"blocks.{b}.fc_1", (g, N[b], omax[2 * b + 1:2 * b + 2], amax[2 * b + 1:2 * b + 2], True, relu_x))]
                 if b == cl and NS > 1 and mlp.combine_type == "average":
                     # the mean's adjoint (torch's MeanBackward: the gradient expanded over the views, / NS)
                     gin = (gin.reshape(SB, 1, B, H).expand(SB, NS, B, H) / NS).reshape(M1, H)   # one pass
@@ -229,37 +232,16 @@ class _FieldTrainLayers(torch.autograd.Function):
                 lat_feat = _gather(fused, hwc, K, NS, p, B, net.d_latent)   # (lookup_features' batched launches)
                 lat_max = fused.latent_max_bits(latent)
                 for b in range(nz):
-                    zmax = Gz_max[b]
-                    wl1.append((Gz[b], lat_feat, zmax, lat_max, True))
+                    wl1.append((f"lin_z.{b}", (Gz[b], lat_feat, Gz_max[b], lat_max, True)))
                 for b in range(nz if spade else 0):
-                    wl1.append((Gs[b], lat_feat, Gs_max[b], lat_max, True))
-            wl1.append((g_in0, zfp, g_in0_max, ops._max_bits(zfp), True))
-            wl2.append((d4, Xpre[nb], d4_max, a_max, True, relu_x))
+                    wl1.append((f"scale_z.{b}", (Gs[b], lat_feat, Gs_max[b], lat_max, True)))
+            wl1.append(("lin_in", (g_in0, zfp, g_in0_max, ops._max_bits(zfp), True)))
+            wl2.append(("lin_out", (d4, Xpre[nb], d4_max, a_max, True, relu_x)))
             if M1 == M2:     # one source view: every layer over the same rows, one launch
-                r = ops.weight_grads(wl1 + wl2, M1)
-                r1, r2 = r[:len(wl1)], r[len(wl1):]
+                grads = tc.named_weight_grads(wl1 + wl2, M1, net.d_in)
             else:
-                r1, r2 = ops.weight_grads(wl1, M1), ops.weight_grads(wl2, M2)
-            grads = {"lin_out.weight": r2[-1][0], "lin_out.bias": r2[-1][1]}
-            i1, i2 = 0, 0
-            for b in range(nb):
-                if b < cl:
-                    (w0, c0), (w1, c1) = r1[i1], r1[i1 + 1]
-                    i1 += 2
-                else:
-                    (w0, c0), (w1, c1) = r2[i2], r2[i2 + 1]
-                    i2 += 2
-                grads[f"blocks.{b}.fc_0.weight"], grads[f"blocks.{b}.fc_0.bias"] = w0, c0
-                grads[f"blocks.{b}.fc_1.weight"], grads[f"blocks.{b}.fc_1.bias"] = w1, c1
-            for b in range(nz):
-                grads[f"lin_z.{b}.weight"], grads[f"lin_z.{b}.bias"] = r1[i1]
-                i1 += 1
-            for b in range(nz if spade else 0):
-                grads[f"scale_z.{b}.weight"], grads[f"scale_z.{b}.bias"] = r1[i1]
-                i1 += 1
-            w_in, c_in = r1[i1]
-            grads["lin_in.weight"], grads["lin_in.bias"] = w_in[:, :net.d_in].contiguous(), c_in
-        g_feat = g_zf = None
+                grads = {**tc.named_weight_grads(wl1, M1, net.d_in), **tc.named_weight_grads(wl2, M2, net.d_in)}
+        g_feat = None
         # with stop_encoder_grad the looked-up latent is detached (models.py:810-811): no gradient reaches the
         # points through the lookup, z_feature's part alone (as avr.field._FieldTrain)
         if (want_latent or want_xyz) and nz > 0 and not net.stop_encoder_grad:
@@ -267,10 +249,8 @@ class _FieldTrainLayers(torch.autograd.Function):
                 pairs = [(Gz[b], P[f"lin_z.{b}.weight"].detach()) for b in range(nz)]
                 pairs += [(Gs[b], P[f"scale_z.{b}.weight"].detach()) for b in range(nz)]
                 g_feat = ops.sum_of_products(pairs)
-            else:   # the lin_z^T layers on the x3 layer GEMM where they apply (avr.field._feat_grad)
-                g_feat = _feat_grad(fused, entry, bwd, Gz, P, M1)
-        if want_xyz:
-            g_zf = g_in0 @ P["lin_in.weight"].detach()
-        d_latent, d_xyz = input_grads(fused, xyz, viewdirs, latent, want_latent, want_xyz, g_feat, g_zf, NS)
-        return (None, None, None, d_xyz, None, d_latent) + tuple(
-            grads[n] if ctx.needs_input_grad[6 + i] else None for i, n in enumerate(names))
+            else:   # the lin_z^T layers on the x3 layer GEMM where they apply (train_common.feat_grad)
+                g_feat = tc.feat_grad(fused, entry, bwd, Gz, P, M1)
+        d_latent, d_xyz = tc.mlp_input_grads(fused, xyz, viewdirs, latent, want_latent, want_xyz, g_feat, g_in0,
+                                             P["lin_in.weight"], NS)
+        return tc.backward_result(ctx.needs_input_grad, names, grads, d_xyz, d_latent)

@@ -9,12 +9,11 @@ launch backward (avr_loss_bwd), against about 15 launches of the torch expressio
 (DESIGN Q9), so loss_fn + backward can be recorded in a torch.cuda.graph (avr.graphs.GraphedTrainStep's step_fn).
 No CPU path: host tensors raise AVRError.
 """
-import ctypes
 import functools
 
 import torch
 
-from ._lib import call, ptr, require_device, stream_of
+from ._lib import call, ptr, require_device, size_query, stream_of
 
 F32 = torch.float32
 COARSE, FINE, DEPTH = 1, 2, 4   # avr.h AVR_LOSS_*
@@ -26,9 +25,7 @@ def _f32c(t):
 
 @functools.lru_cache(maxsize=64)
 def _workspace_bytes(n):
-    out = ctypes.c_int64()
-    call("avr_loss_workspace_bytes", n, ctypes.byref(out))
-    return out.value
+    return size_query("avr_loss_workspace_bytes", n)
 
 
 def loss_terms(loss_params):

@@ -4,12 +4,11 @@ skimage.metrics. Here one HIP launch covers every frame (avr_image_metrics: 7 x 
 moments, PSNR from the same staged pixels) and only the two reported scalars cross to the host. No CPU path: host
 tensors raise AVRError.
 """
-import ctypes
 import math
 
 import torch
 
-from ._lib import call, ptr, require_device, stream_of
+from ._lib import call, ptr, require_device, size_query, stream_of
 
 F32 = torch.float32
 
@@ -30,9 +29,7 @@ def image_metrics(img, gt, H, W):
     B = img.numel() // (H * W * 3)
     img, gt = _f32c(img.detach()), _f32c(gt.detach())
     require_device(img, gt)
-    n_bytes = ctypes.c_int64()
-    call("avr_image_metrics_workspace_bytes", B, H, W, ctypes.byref(n_bytes))
-    ws = torch.empty(n_bytes.value, device=img.device, dtype=torch.uint8)
+    ws = torch.empty(size_query("avr_image_metrics_workspace_bytes", B, H, W), device=img.device, dtype=torch.uint8)
     out = torch.empty(2, B, device=img.device, dtype=F32)
     call("avr_image_metrics", ptr(img), ptr(gt), B, H, W, ptr(ws), ws.numel(), ptr(out[0]), ptr(out[1]),
          stream_of(img))

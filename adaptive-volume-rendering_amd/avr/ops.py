@@ -257,9 +257,7 @@ def march_fine(ro, rd, z, field_fn, t_stop, white_back=True, infinity=1.8, chunk
     ro, rd, z = _f32c(ro.reshape(R, 3)), _f32c(rd.reshape(R, 3)), _f32c(z)
     require_device(ro, rd, z)
     dev, s = z.device, stream_of(z)
-    nbytes = ctypes.c_int64()
-    call("avr_march_state_bytes", R, ctypes.byref(nbytes))
-    state = torch.empty(max(nbytes.value, 8), device=dev, dtype=torch.uint8)
+    state = torch.empty(max(_lib.size_query("avr_march_state_bytes", R), 8), device=dev, dtype=torch.uint8)
     active = torch.empty(max(R, 1), device=dev, dtype=torch.int32)
     spare = torch.empty_like(active)
     count = torch.zeros(1, device=dev, dtype=torch.int32)
@@ -606,16 +604,12 @@ def latent_features_adjoint(views, xyz, grad_features, hw):
     require_device(xyz)
     ld = grad_features.stride(0) if grad_features.shape[0] > 1 else C
     out = torch.empty(n_scenes, H * W, C, device=xyz.device, dtype=F32)
-    lib = _lib.load()
     for g0, n in _lib.scene_groups(n_scenes):
         vs = views if n == n_scenes else (_lib.ViewDesc * n)(*views[g0:g0 + n])
-        nb = ctypes.c_int64(0)
-        _lib.check(lib.avr_latent_features_adjoint_scratch_bytes(n, n_points, H, W, C, ctypes.byref(nb)),
-                   "avr_latent_features_adjoint_scratch_bytes")
-        scratch = torch.empty(max(nb.value, 16), device=xyz.device, dtype=torch.uint8)
-        call("avr_latent_features_adjoint", vs, n, ptr(xyz[g0]), n_points,
-             ctypes.c_void_p(grad_features.data_ptr() + g0 * n_points * ld * 4), ld, C, ptr(out[g0]), ptr(scratch),
-             nb.value, stream_of(xyz))
+        nb = _lib.size_query("avr_latent_features_adjoint_scratch_bytes", n, n_points, H, W, C)
+        scratch = torch.empty(max(nb, 16), device=xyz.device, dtype=torch.uint8)
+        call("avr_latent_features_adjoint", vs, n, ptr(xyz[g0]), n_points, ptr(grad_features, g0 * n_points * ld), ld,
+             C, ptr(out[g0]), ptr(scratch), nb, stream_of(xyz))
     return out
 
 

@@ -563,10 +563,8 @@ class _MarchTrain(torch.autograd.Function):
             # in a fixed order; no floating-point atomics
             d_tab = torch.empty(tables.shape, device=rd.device, dtype=torch.float32)
             d_grads = torch.empty(64 * 16 + 64 + 16 + 1, device=rd.device, dtype=torch.float32)
-            nb = ctypes.c_int64(0)
-            _lib.check(_lib.load().avr_raymarch_bwd_scratch_bytes(n, ctx.steps, tables.numel(), ctypes.byref(nb)),
-                       "avr_raymarch_bwd_scratch_bytes")
-            scratch = torch.empty(max(nb.value, 1), device=rd.device, dtype=torch.uint8)
+            nb = _lib.size_query("avr_raymarch_bwd_scratch_bytes", n, ctx.steps, tables.numel())
+            scratch = torch.empty(max(nb, 1), device=rd.device, dtype=torch.uint8)
             gw = grad_world.float().reshape(n, 3).contiguous()
             stop = bool(getattr(ctx.phi, "stop_encoder_grad", False))   # detached lookup: no position gradient
             _lib.call("avr_raymarch_bwd", ctx.views, SB, _lib.ptr(tables), _lib.ptr(P[0]), _lib.ptr(P[3]),

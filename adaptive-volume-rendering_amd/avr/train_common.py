@@ -1,17 +1,59 @@
 """What the three training Functions share (avr.field._FieldTrain, avr.bn_train._FieldTrainBN,
-avr.layer_train._FieldTrainLayers): the rf(xyz, viewdirs, coarse) entry, the layer paths' padded z_feature
-operand and lin_z epilogue, the interpolated-latent lookup and the input gradients: the latent maps' through the
-lookup's HIP adjoint (avr_latent_features_adjoint), the rest through torch autograd of net.mlp_inputs. Nothing here
-imports avr.field: a FusedField comes in as an argument."""
+avr.layer_train._FieldTrainLayers): the rf(xyz, viewdirs, coarse) entry, the layer runner (avr_bn_layer_run) with
+the feature gradient on its lin_z^T layers, the layer paths' padded z_feature operand and lin_z epilogue, the
+weight gradients by parameter name, the interpolated-latent lookup, the input gradients -- the latent maps' through
+the lookup's HIP adjoint (avr_latent_features_adjoint), the rest through torch autograd of net.mlp_inputs -- and
+the backward's return tuple. Nothing here imports avr.field: a FusedField comes in as an argument. The Functions
+call the runner through this module (train_common.run_layer), so a test or a diagnostic replaces it here."""
 import ctypes
 import os
 
 import torch
 
-from . import ops
-from ._lib import call, ptr, scene_groups, stream_of
+from . import _lib, ops
+from ._lib import BnLayer, call, ptr, scene_groups, size_query, stream_of
 
 F32 = torch.float32
+
+
+def bn_layer(**kw):
+    """An avr_bn_layer from keyword fields (tensors become their device addresses)."""
+    l = BnLayer()
+    for k, v in kw.items():
+        setattr(l, k, v.data_ptr() if isinstance(v, torch.Tensor) else v)
+    return l
+
+
+def run_layer(dims, layer, stream):
+    call("avr_bn_layer_run", ctypes.byref(dims), ctypes.byref(layer), stream)
+
+
+def layer_partial(M, H, dev):
+    """The per-workgroup column partials of avr_bn_layer_run plus the fold scratch of avr_bn_stats."""
+    return torch.empty(size_query("avr_bn_partial_floats", M, H), device=dev, dtype=F32)
+
+
+def feat_grad(fused, entry, bwd, Gz, P, Mt):
+    """The looked-up latent features' gradient sum_b Gz[b] . W_z[b] (the point / latent gradients' input):
+    avr_bn_layer_run's lin_z[b]^T layers from the backward blob (x3, ABI 14), one launch per layer adding the
+    previous layers' sum in its epilogue, where they apply (d_latent == d_hidden, ReLU, 64..512 wide); else
+    fp32 library GEMMs (avr.ops.sum_of_products). entry: anything holding the blob's dims (an x3 copy is made)."""
+    dims = entry.dims.with_precision(_lib.FIELD_X3)
+    H, nz = dims.d_hidden, dims.n_lin_z
+    if not (dims.d_latent == H and H in (64, 128, 256, 512) and not dims.spade and not dims.bn
+            and not dims.beta > 0 and Mt > 0 and all(g.is_contiguous() for g in Gz)):
+        return ops.sum_of_products([(Gz[b], P[f"lin_z.{b}.weight"].detach()) for b in range(nz)])
+    dev = Gz[0].device
+    part = layer_partial(Mt, H, dev)
+    stream = stream_of(Gz[0])
+    prev = None
+    for b in range(nz):
+        out = torch.empty(Mt, H, device=dev, dtype=F32)
+        run_layer(dims, bn_layer(n_rows=Mt, mode=_lib.BN_BWD, prologue=_lib.BN_PLAIN, in_dim=H, in_valid=H, src=Gz[b],
+                                 ld_src=H, blob=bwd, layer=_lib.BN_LAYER_LIN_Z_T + b, add1=prev, out=out,
+                                 partial=part), stream)
+        prev = out
+    return prev
 
 
 def forward_train(fused, xyz, viewdirs, coarse, function, param_names):
@@ -41,6 +83,22 @@ def lin_z_epilogue(tables, b, nz, p, views, n_views, B):
         return {}
     return dict(lin_z_table=tables[0, b], lin_z_scene_stride=tables.stride(0), xyz=p,
                 views=ctypes.addressof(views), n_views=n_views, rows_per_scene=B)
+
+
+def named_weight_grads(named_layers, n_rows, d_in, specs_on=None):
+    """One avr_weight_grads launch sequence over `named_layers`, (module name, layer) pairs in launch order (the
+    order decides the chunking and, through the tile count, the K-split) -> {name + ".weight": dW, name + ".bias":
+    db (None for a layer without want_bias)}. layer: an ops.weight_grads tuple, or with specs_on = (device, stream)
+    an ops.weight_grads_specs integer spec. lin_in's operand rows are z_feature padded to 16 B: its dW keeps the
+    first d_in columns."""
+    layers = [layer for _, layer in named_layers]
+    res = ops.weight_grads(layers, n_rows) if specs_on is None else ops.weight_grads_specs(layers, n_rows, *specs_on)
+    grads = {}
+    for (name, _), (dW, db) in zip(named_layers, res):
+        grads[name + ".weight"], grads[name + ".bias"] = dW, db
+    if "lin_in.weight" in grads:
+        grads["lin_in.weight"] = grads["lin_in.weight"][:, :d_in].contiguous()
+    return grads
 
 
 def gather_rows(fused, tab, K, NS, p, B, C):
@@ -132,3 +190,17 @@ def input_grads_via_autograd(net, xyz, viewdirs, latent, want_latent, want_xyz, 
     if want_xyz:
         d_xyz = res[-1] if res[-1] is not None else torch.zeros_like(xyz)
     return d_latent, d_xyz
+
+
+def mlp_input_grads(fused, xyz, viewdirs, latent, want_latent, want_xyz, g_feat, g_in0, w_in, ns=1):
+    """(d_latent, d_xyz) as input_grads, from the gradient g_in0 at lin_in's output (z_feature's is g_in0 . w_in,
+    formed when the points want one) and the looked-up features' g_feat, which each path forms its own way."""
+    g_zf = g_in0 @ w_in.detach() if want_xyz else None
+    return input_grads(fused, xyz, viewdirs, latent, want_latent, want_xyz, g_feat, g_zf, ns)
+
+
+def backward_result(needs_input_grad, names, grads, d_xyz, d_latent):
+    """A training Function's backward result for its inputs (fused, coarse, names, xyz, viewdirs, latent,
+    *params): grads[name] for each parameter of `names` that wants a gradient."""
+    return (None, None, None, d_xyz, None, d_latent) + tuple(
+        grads[n] if needs_input_grad[6 + i] else None for i, n in enumerate(names))

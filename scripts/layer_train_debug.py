@@ -12,7 +12,7 @@ for p in (REPO, os.path.join(REPO, "adaptive-volume-rendering_amd"), os.path.joi
 
 
 def main():
-    from avr import _lib, bn_train, layer_train
+    from avr import _lib, layer_train, train_common
     from test_gpu_layer_train import _views_net
     a = sys.argv[1:] or ["64", "3", "64", "2", "2", "2", "1", "average"]
     d_hidden, n_blocks, d_latent, cl, SB, NS, spade = (int(x) for x in a[:7])
@@ -24,7 +24,7 @@ def main():
     vd = torch.nn.functional.normalize(torch.randn(SB, B, 3, generator=g), dim=-1).to(dev)
     w = torch.randn(SB, B, 4, generator=g).to(dev)
     cur = {"mlp": net.mlp_coarse}
-    orig_layer, orig_run = bn_train._layer, bn_train._run
+    orig_layer, orig_run = train_common.bn_layer, train_common.run_layer
     calls = []
     snaps = {}
 
@@ -86,13 +86,13 @@ def main():
         wg_calls.append([l[0].clone() for l in layers])
         return orig_wg(layers, n_rows, n_split)
 
-    bn_train._layer, bn_train._run = layer, run
+    train_common.bn_layer, train_common.run_layer = layer, run
     layer_train._gather = gather
     ops.weight_grads = wg
     try:
         gh = grads(True, False)
     finally:
-        bn_train._layer, bn_train._run = orig_layer, orig_run
+        train_common.bn_layer, train_common.run_layer = orig_layer, orig_run
         layer_train._gather = orig_gather
         ops.weight_grads = orig_wg
     # torch reference of the gradients at every block input (after the spade product), by hand

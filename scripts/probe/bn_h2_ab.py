@@ -13,7 +13,7 @@ sys.path.insert(0, os.path.join(REPO, "adaptive-volume-rendering_amd"))
 
 def main():
     from avr import _lib
-    from avr.bn_train import _layer, _partial, _run
+    from avr.train_common import bn_layer as _layer, layer_partial as _partial, run_layer as _run
     from avr.conf import Conf, default_conf
     from avr.scene import synthetic_scene
     dev = torch.device("cuda:0")

@@ -4,7 +4,7 @@ then. No kernel is launched: the wrapped callable here is a stand-in."""
 import pytest
 import torch
 
-from avr import anomaly, bn_train, field, ops, renderers
+from avr import anomaly, bn_train, field, layer_train, ops, renderers
 
 
 def test_every_hook_installed():
@@ -13,8 +13,8 @@ def test_every_hook_installed():
     for n in anomaly.FIELD_METHODS:
         assert getattr(getattr(field.FusedField, n), "__avr_checked__", False), n
     for m, c in anomaly.FUNCTIONS:
-        assert getattr(getattr({"ops": ops, "field": field, "bn_train": bn_train,
-                                                "renderers": renderers}[m], c).backward, "__avr_checked__", False), c
+        assert getattr(getattr({"ops": ops, "field": field, "bn_train": bn_train, "layer_train": layer_train,
+                                "renderers": renderers}[m], c).backward, "__avr_checked__", False), c
     anomaly.install()   # idempotent: no double wrapping
     assert not getattr(ops.world_rays.__wrapped__, "__avr_checked__", False)
 

@@ -8,7 +8,7 @@ module (models.py:541-592, 739-863). The kernels themselves are held to float64 
 import pytest
 import torch
 
-from avr import _lib, bn_train, field, layer_train, ops
+from avr import _lib, layer_train, ops, train_common
 
 
 def _net(d_hidden, n_blocks, d_latent, cl, SB, NS, spade, ctype, hw=(6, 7), seed=0):
@@ -158,10 +158,10 @@ def _install(monkeypatch, net):
     monkeypatch.setattr(fused, "tables_batch", tables_batch)
     monkeypatch.setattr(layer_train, "_gather", gather)
     monkeypatch.setattr(layer_train, "stream_of", lambda t: None)
-    monkeypatch.setattr(field, "stream_of", lambda t: None)
-    monkeypatch.setattr(bn_train, "_layer", lambda **kw: kw)
-    monkeypatch.setattr(bn_train, "_run", run)
-    monkeypatch.setattr(bn_train, "_partial", lambda M, H, dev: torch.empty(1))
+    monkeypatch.setattr(train_common, "stream_of", lambda t: None)
+    monkeypatch.setattr(train_common, "bn_layer", lambda **kw: kw)
+    monkeypatch.setattr(train_common, "run_layer", run)
+    monkeypatch.setattr(train_common, "layer_partial", lambda M, H, dev: torch.empty(1))
     monkeypatch.setattr(ops, "weight_grads", weight_grads)
     return fused
 
