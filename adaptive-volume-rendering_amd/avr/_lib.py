@@ -105,6 +105,15 @@ class AdamTensor(ctypes.Structure):
                 ("numel", i64)]
 
 
+OCC_MAX_RES = 256       # avr.h AVR_OCC_MAX_RES: cells per axis of an occupancy grid
+OCC_MAX_SAMPLES = 256   # avr.h AVR_OCC_MAX_SAMPLES: samples per ray of avr_occ_classify / _compact / _expand
+
+
+class OccGrid(ctypes.Structure):
+    """avr_occ_grid: the box's low corner, cells per unit length, resolution (rx, ry, rz) and the device bits."""
+    _fields_ = [("lo", c_float * 3), ("inv", c_float * 3), ("res", c_int * 3), ("bits", c_void_p)]
+
+
 # name -> argtypes (all return int status)
 _SIGS = {
     "avr_world_rays": [c_void_p, c_void_p, c_void_p, i64, i64, i64, i64, c_void_p, c_void_p, c_void_p],
@@ -200,6 +209,12 @@ _SIGS = {
     # tensors: an AdamTensor array, or the address of one (c_void_p takes both)
     "avr_adam_step": [c_void_p, i64, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double,
                       ctypes.c_double, c_void_p, c_void_p],
+    "avr_occ_build": [c_void_p, c_int, ctypes.POINTER(c_int), c_float, c_int, c_void_p, c_void_p],
+    "avr_occ_classify": [ctypes.POINTER(OccGrid), c_void_p, c_void_p, c_void_p, i64, c_int, c_void_p, c_void_p,
+                         c_void_p],
+    "avr_occ_compact": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, i64, c_int, i64, c_void_p, c_void_p,
+                        c_void_p],
+    "avr_occ_expand": [c_void_p, c_void_p, c_void_p, i64, c_int, i64, c_void_p, c_void_p],
     "avr_stream_copy": [c_void_p, c_void_p, i64, c_void_p],
     "avr_stream_fill": [c_void_p, i64, c_uint32, c_void_p],
 }

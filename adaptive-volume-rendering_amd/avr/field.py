@@ -498,14 +498,24 @@ class FusedField:
                 call("avr_field_fwd_points_batch", ctypes.byref(dims), views, n, ptr(entry.packed),
                      ptr(tables[g0]), ptr(p[g0]), ptr(v[g0]), B, ptr(out[g0]), stream_of(p))
             return out
-        dims = entry.dims_as(PRECISIONS[self.precision])
         for sb in range(SB):
-            p = xyz[sb].to(F32).contiguous()
-            v = viewdirs.reshape(SB, B, 3)[sb].to(F32).contiguous()
-            require_device(p, v)
-            table = self.table(coarse, sb)
-            call("avr_field_fwd_points", ctypes.byref(dims), ctypes.byref(self.view(sb)), ptr(entry.packed),
-                 ptr(table), ptr(p), ptr(v), B, ptr(out[sb]), stream_of(p))
+            self.forward_points_scene(xyz[sb], viewdirs.reshape(SB, B, 3)[sb], coarse, sb, out=out[sb])
+        return out
+
+    def forward_points_scene(self, xyz, viewdirs, coarse, sb=0, out=None):
+        """Scene sb's field at a point list: xyz, viewdirs (M, 3) -> (M, 4), one avr_field_fwd_points launch with
+        that scene's view and lin_z tables (single-view nets)."""
+        M = xyz.shape[0]
+        p = xyz.to(F32).contiguous()
+        v = viewdirs.to(F32).contiguous()
+        require_device(p, v)
+        if out is None:
+            out = torch.empty(M, 4, device=p.device, dtype=F32)
+        entry = self.packed(coarse)
+        dims = entry.dims_as(PRECISIONS[self.precision])
+        table = self.table(coarse, sb)
+        call("avr_field_fwd_points", ctypes.byref(dims), ctypes.byref(self.view(sb)), ptr(entry.packed),
+             ptr(table), ptr(p), ptr(v), M, ptr(out), stream_of(p))
         return out
 
     # ----------------------------------------------------------- training

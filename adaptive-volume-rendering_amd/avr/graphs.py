@@ -49,6 +49,9 @@ class GraphedRenderer:
     def __init__(self, renderer, net, cam2world, intrinsics, x_pix, warmup=2):
         if renderer.t_stop is not None:
             raise ValueError("GraphedRenderer: early termination sizes its launches on the host (t_stop must be None)")
+        if getattr(renderer, "occupancy", None) is not None:
+            raise ValueError("GraphedRenderer: occupancy gating reads the live count back to the host "
+                             "(renderer.occupancy must be None)")
         if hasattr(renderer, "stage_host_draws") and renderer.seed is None:
             raise ValueError("GraphedRenderer: the adaptive renderers draw their start distances on the host "
                              "unless seeded (set renderer.seed)")

@@ -1,0 +1,202 @@
+"""Occupancy-grid empty-space skipping for VolumeRenderer inference (not in the reference; DESIGN.md "Occupancy
+grid", include/avr.h "occupancy grid").
+
+    grid = OccupancyGrid.from_field(net, lo=(-1, -1, -1), hi=(1, 1, 1), res=(128, 128, 128))
+    renderer.occupancy = grid                     # or a list with one grid per scene; None (default): ungated
+    rgb_c, rgb_f, depth, _ = renderer(cam2world, intrinsics, x_pix, net)      # under torch.no_grad()
+
+A grid is a bit per cell of an axis-aligned box. A sample whose point falls in a clear cell, or outside the box, is
+not evaluated: the composite sees exactly 0.0 in all four channels for it (sigma = 0). The live samples are compacted
+in ray-major sample order, evaluated by one avr_field_fwd_points launch and scattered back (gated_field): classify
+-> cumsum -> one host read of the live count -> compact -> field -> expand. The host read makes the path eager only:
+it cannot be recorded in a HIP-graph capture.
+
+What the render loses is what the grid calls empty. from_field marks a cell from sigma at its centre alone, for a
+handful of view directions, so a density feature thinner than a cell, or one that only other view directions see, can
+be missed: `dilate` (cells of safety margin around every occupied cell) and `sigma_thr` trade that risk against the
+live share. sigma_thr = 0.0 (the default) keeps every cell where any evaluated sigma is above exactly zero after the
+ReLU; a positive threshold also drops faint fog, which changes the image by up to the weight that fog carried.
+"""
+import ctypes
+
+import numpy as np
+import torch
+
+from . import _lib
+from ._lib import OccGrid, call, ptr, require_device, stream_of
+from .cache import _version_key
+
+F32 = torch.float32
+AXIS_DIRS = ((1.0, 0.0, 0.0), (-1.0, 0.0, 0.0), (0.0, 1.0, 0.0), (0.0, -1.0, 0.0), (0.0, 0.0, 1.0), (0.0, 0.0, -1.0))
+
+
+def _check_res(res):
+    res = tuple(int(r) for r in res)
+    if len(res) != 3 or not all(1 <= r <= _lib.OCC_MAX_RES for r in res) or res[0] % 32:
+        raise ValueError(f"occupancy grid resolution {res}: three values in 1..{_lib.OCC_MAX_RES}, the first a "
+                         "multiple of 32")
+    return res
+
+
+def n_words(res):
+    return (res[0] // 32) * res[1] * res[2]
+
+
+def field_key(net):
+    """The version key (avr.cache) of everything the field's values depend on: the parameters and buffers of both
+    MLPs, the latent map, the source views. Returns (key, the tensors whose addresses are part of it)."""
+    fused = net.fused()
+    mlps = [net.mlp_coarse] + ([net.mlp_fine] if net.mlp_fine is not None else [])
+    ts = []
+    for mlp in mlps:
+        _, ps, bs = fused._state(mlp)
+        ts += ps + bs
+    lat = net.encoder.latent
+    srcs = fused._view_sources()
+    return (_version_key(ts + [lat]), _version_key(srcs, gen=False), tuple(lat.shape)), ts + [lat] + srcs
+
+
+class OccupancyGrid:
+    """The descriptor and the device bits of one scene's grid: box [lo, hi), res = (rx, ry, rz) cells, bits an int32
+    tensor of rx / 32 * ry * rz words (cell (ix, iy, iz) = bit ix % 32 of word (iz * ry + iy) * (rx / 32) + ix / 32).
+    key: the field_key() of the net it was built from (from_field), or None for a grid that no net's state can
+    make stale (from_sigma, all_occupied)."""
+
+    def __init__(self, lo, hi, res, bits, key=None, keep=None):
+        self.res = _check_res(res)
+        self.lo = tuple(float(np.float32(v)) for v in lo)
+        self.hi = tuple(float(np.float32(v)) for v in hi)
+        if len(self.lo) != 3 or len(self.hi) != 3 or not all(h > l for l, h in zip(self.lo, self.hi)):
+            raise ValueError(f"occupancy grid box lo {self.lo} hi {self.hi}: need hi > lo on three axes")
+        if bits.dtype != torch.int32 or bits.numel() != n_words(self.res):
+            raise ValueError(f"occupancy grid bits: {n_words(self.res)} int32 words for res {self.res}")
+        self.bits = bits.reshape(-1).contiguous()
+        self.key, self._keep = key, keep
+        self.inv = tuple(float(np.float32(r / (float(h) - float(l)))) for r, l, h in zip(self.res, self.lo, self.hi))
+        self.desc = OccGrid((ctypes.c_float * 3)(*self.lo), (ctypes.c_float * 3)(*self.inv),
+                            (ctypes.c_int * 3)(*self.res), self.bits.data_ptr())
+
+    @property
+    def device(self):
+        return self.bits.device
+
+    def live_fraction(self):
+        """Share of the cells whose bit is set (a host read of the bits)."""
+        words = self.bits.cpu().numpy().view(np.uint8)
+        return float(np.unpackbits(words).sum()) / float(self.res[0] * self.res[1] * self.res[2])
+
+    def stale(self, net):
+        """True when the grid was built from a net's field (from_field) and `net`'s parameters, latent map or source
+        views are no longer the ones it was built from."""
+        return self.key is not None and self.key != field_key(net)[0]
+
+    @classmethod
+    def all_occupied(cls, lo, hi, res, device):
+        res = _check_res(res)
+        return cls(lo, hi, res, torch.full((n_words(res),), -1, dtype=torch.int32, device=device))
+
+    @classmethod
+    def from_sigma(cls, sigma_planes, lo, hi, thr, dilate=1, key=None, keep=None):
+        """sigma_planes (K, rz, ry, rx) or (rz, ry, rx) fp32 on the device: a cell is set iff any plane at any cell
+        within Chebyshev distance `dilate` (0, 1 or 2, clamped at the box faces) has not (sigma <= thr); NaN counts
+        as occupied (avr_occ_build)."""
+        s = sigma_planes if sigma_planes.dim() == 4 else sigma_planes[None]
+        if s.dim() != 4 or s.shape[0] < 1:
+            raise ValueError("from_sigma: sigma_planes must be (K, rz, ry, rx) or (rz, ry, rx)")
+        if int(dilate) not in (0, 1, 2):
+            raise ValueError("from_sigma: dilate must be 0, 1 or 2")
+        res = _check_res((s.shape[3], s.shape[2], s.shape[1]))
+        s = s.to(F32).contiguous()
+        require_device(s)
+        bits = torch.empty(n_words(res), dtype=torch.int32, device=s.device)
+        call("avr_occ_build", ptr(s), s.shape[0], (ctypes.c_int * 3)(*res), float(thr), int(dilate), ptr(bits),
+             stream_of(s))
+        return cls(lo, hi, res, bits, key, keep)
+
+    @staticmethod
+    def cell_centres(lo, hi, res, device):
+        """(rz * ry * rx, 3) fp32 cell centres, x fastest: lo + (i + 0.5) * cell in float64, then rounded."""
+        ax = [np.float32(l).astype(np.float64) + (np.arange(r, dtype=np.float64) + 0.5)
+              * ((np.float32(h).astype(np.float64) - np.float32(l).astype(np.float64)) / r)
+              for l, h, r in zip(lo, hi, res)]
+        zz, yy, xx = np.meshgrid(ax[2], ax[1], ax[0], indexing="ij")
+        return torch.from_numpy(np.stack([xx, yy, zz], -1).reshape(-1, 3).astype(np.float32)).to(device)
+
+    @classmethod
+    def from_field(cls, net, lo, hi, res=(128, 128, 128), sigma_thr=0.0, dilate=1, dirs=None, sb=0, chunk=1 << 20):
+        """The grid of scene `sb` of a fusable NewPixelNeRFNet: sigma (output channel 3) of both MLPs, coarse and
+        fine if present, at every cell centre for every view direction in `dirs` (default: the six axis directions
+        -- the MLP sees the view direction, so one is not enough), `chunk` points per field launch, then from_sigma
+        over all those planes. The grid records the field_key() it was built under (stale())."""
+        from .field import fused_eligible
+        if not fused_eligible(net):
+            raise ValueError("OccupancyGrid.from_field: the net is not on the single-view fused path")
+        res = _check_res(res)
+        dev = net.encoder.latent.device
+        fused = net.fused()
+        dirs = AXIS_DIRS if dirs is None else dirs
+        passes = [True] + ([False] if net.mlp_fine is not None else [])
+        key, keep = field_key(net)
+        with torch.no_grad():
+            centres = cls.cell_centres(lo, hi, res, dev)
+            n = centres.shape[0]
+            planes = torch.empty(len(passes) * len(dirs), n, device=dev, dtype=F32)
+            k = 0
+            for coarse in passes:
+                for d in dirs:
+                    vd = torch.tensor([d], device=dev, dtype=F32)
+                    for c0 in range(0, n, int(chunk)):
+                        p = centres[c0:c0 + int(chunk)]
+                        out = fused.forward_points_scene(p, vd.expand(p.shape[0], 3), coarse, sb)
+                        planes[k, c0:c0 + p.shape[0]] = out[:, 3]
+                    k += 1
+            return cls.from_sigma(planes.reshape(-1, res[2], res[1], res[0]), lo, hi, sigma_thr, dilate, key, keep)
+
+
+def classify(grid, ro, rd, z):
+    """avr_occ_classify: ro, rd (R, 3), z (R, N) -> mask (R, ceil(N / 64)) int64 (the uint64 words' bits), counts
+    (R,) int32."""
+    R, N = z.shape
+    require_device(ro, rd, z, grid.bits)
+    mask = torch.empty(R, (N + 63) // 64, device=z.device, dtype=torch.int64)
+    counts = torch.empty(R, device=z.device, dtype=torch.int32)
+    call("avr_occ_classify", ctypes.byref(grid.desc), ptr(ro), ptr(rd), ptr(z), R, N, ptr(mask), ptr(counts),
+         stream_of(z))
+    return mask, counts
+
+
+def compact(ro, rd, z, mask, offsets, n_live):
+    """avr_occ_compact -> xyz, viewdirs (n_live, 3) of the live samples, ray-major sample order."""
+    R, N = z.shape
+    xyz = torch.empty(n_live, 3, device=z.device, dtype=F32)
+    vd = torch.empty_like(xyz)
+    call("avr_occ_compact", ptr(ro), ptr(rd), ptr(z), ptr(mask), ptr(offsets), R, N, n_live, ptr(xyz), ptr(vd),
+         stream_of(z))
+    return xyz, vd
+
+
+def expand(field_c, mask, offsets, R, N, n_live):
+    """avr_occ_expand: field_c (n_live, 4) or None -> (R * N, 4), zeros for dead samples, every element written."""
+    field = torch.empty(R * N, 4, device=mask.device, dtype=F32)
+    call("avr_occ_expand", ptr(field_c), ptr(mask), ptr(offsets), R, N, n_live, ptr(field), stream_of(field))
+    return field
+
+
+def gated_field(fused, grid, ro, rd, z, coarse, sb=0):
+    """The field of scene `sb` at ro[r] + rd[r] * z[r, s] where `grid` is live, exactly zero elsewhere:
+    (field (R * N, 4), n_live). One host read (the live count); no field launch when nothing is live."""
+    R, N = z.shape
+    if z.is_cuda and torch.cuda.is_current_stream_capturing():
+        raise ValueError("occupancy gating reads the live count back to the host: it cannot be captured in a graph")
+    ro = ro.reshape(R, 3).to(F32).contiguous()
+    rd = rd.reshape(R, 3).to(F32).contiguous()
+    z = z.to(F32).contiguous()
+    mask, counts = classify(grid, ro, rd, z)
+    incl = torch.cumsum(counts, 0, dtype=torch.int64)
+    offsets = incl - counts
+    n_live = int(incl[-1].item()) if R else 0
+    field_c = None
+    if n_live:
+        xyz, vd = compact(ro, rd, z, mask, offsets, n_live)
+        field_c = fused.forward_points_scene(xyz, vd, coarse, sb)
+    return expand(field_c, mask, offsets, R, N, n_live), n_live

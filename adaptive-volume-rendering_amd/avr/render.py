@@ -4,6 +4,7 @@ harness, utils.py:481-537, on the fused path; BASELINE configs 4 and 5).
     python -m avr.render --frames 4 --res 800 [--t-stop 1e-5] [--out DIR]
     torchrun --nproc-per-node N -m avr.render ...   # rays of every frame sharded over N GPUs
     python -m avr.render --renderer adaptive --n-coarse 20 --philox-seed 3   # in-kernel draws: reproducible frames
+    python -m avr.render --occupancy 128 [--occupancy-sigma 0.0]   # skip empty space (avr.occupancy); prints the live share
 
 Renders `--frames` views on the reference's camera ring (radius, height 0.4)
 of the synthetic scene (avr.scene) or of a NewPixelNeRFNet state_dict
@@ -73,8 +74,18 @@ def main(argv=None):
     ap.add_argument("--philox-seed", type=int, default=None,
                     help="adaptive renderer: in-kernel Philox draws with this seed (default: the reference's "
                          "torch draws); a sharded frame then does not depend on the number of ranks")
+    ap.add_argument("--occupancy", type=int, default=None, metavar="RES",
+                    help="volume renderer: skip empty space with a RES^3 occupancy grid built from the field once "
+                         "before the frames (avr.occupancy; RES a multiple of 32, at most 256)")
+    ap.add_argument("--occupancy-sigma", type=float, default=0.0, metavar="THR",
+                    help="a cell is empty when sigma <= THR at its centre for both MLPs and six view directions "
+                         "(default 0.0: exactly zero after the ReLU), before one cell of dilation")
+    ap.add_argument("--occupancy-box", type=float, default=1.0, metavar="HALF",
+                    help="the grid covers [-HALF, HALF]^3; samples outside it count as empty")
     ap.add_argument("--out", default=None, help="directory for frame_XXX.ppm")
     args = ap.parse_args(argv)
+    if args.occupancy is not None and (args.renderer != "volume" or args.t_stop is not None):
+        ap.error("--occupancy needs --renderer volume and no --t-stop")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -109,6 +120,11 @@ def main(argv=None):
         rend.seed = 1234
         rend.t_stop = args.t_stop
         samples_per_ray = args.n_coarse + args.n_fine
+        if args.occupancy is not None:   # once per scene, before the frames (after the broadcast: every rank's own)
+            from .occupancy import OccupancyGrid
+            h = args.occupancy_box
+            rend.occupancy = OccupancyGrid.from_field(net, (-h, -h, -h), (h, h, h), (args.occupancy,) * 3,
+                                                      sigma_thr=args.occupancy_sigma)
     K = torch.tensor([INTRINSICS], device=device)
     H = W = args.res
     x_pix = get_opencv_pixel_coordinates(H, W).reshape(1, -1, 2).to(device)
@@ -130,35 +146,43 @@ def main(argv=None):
     torch.cuda.synchronize()
     if dist is not None:
         dist.barrier()
-    fine_samples = 0
+    fine_samples = live_samples = 0
     t0 = time.perf_counter()
     frames = []
     for c2w in poses:
         rend.last_fine_samples = 0
         _, rgb_f, _, _ = render(c2w)
         fine_samples += getattr(rend, "last_fine_samples", 0)
+        live_samples += getattr(rend, "last_live_samples", 0)
         frames.append(rgb_f)
     torch.cuda.synchronize()
     if dist is not None:
         dist.barrier()
     secs = time.perf_counter() - t0
     if dist is not None:
-        t = torch.tensor([secs, float(fine_samples)], device=device, dtype=torch.float64)
+        t = torch.tensor([secs, float(fine_samples), float(live_samples)], device=device, dtype=torch.float64)
         dist.all_reduce(t[:1], op=dist.ReduceOp.MAX)
         dist.all_reduce(t[1:], op=dist.ReduceOp.SUM)
-        secs, fine_samples = float(t[0]), int(t[1])
+        secs, fine_samples, live_samples = float(t[0]), int(t[1]), int(t[2])
     if rank == 0:
         if args.out:
             os.makedirs(args.out, exist_ok=True)
             for i, f in enumerate(frames):
                 write_ppm(os.path.join(args.out, f"frame_{i:03d}.ppm"), to_uint8(f[0].reshape(H, W, 3).cpu().numpy()))
         total_fine = args.frames * n * (args.n_coarse + args.n_fine)
-        print(json.dumps({"renderer": args.renderer, "samples_per_ray": samples_per_ray,
-                          "frames": args.frames, "res": args.res, "rays_per_frame": n, "n_gpus": world,
-                          "seconds": round(secs, 4), "rays_per_s": round(args.frames * n / secs, 1),
-                          "t_stop": args.t_stop, "precision": args.precision, "sigma_bias": args.sigma_bias,
-                          "fine_samples_evaluated": fine_samples,
-                          "fine_samples_fraction": round(fine_samples / total_fine, 4)}), flush=True)
+        line = {"renderer": args.renderer, "samples_per_ray": samples_per_ray,
+                "frames": args.frames, "res": args.res, "rays_per_frame": n, "n_gpus": world,
+                "seconds": round(secs, 4), "rays_per_s": round(args.frames * n / secs, 1),
+                "t_stop": args.t_stop, "precision": args.precision, "sigma_bias": args.sigma_bias,
+                "fine_samples_evaluated": fine_samples,
+                "fine_samples_fraction": round(fine_samples / total_fine, 4)}
+        if args.occupancy is not None:
+            # the live share: field samples evaluated over both passes' n_coarse + (n_coarse + n_fine) per ray
+            line.update({"occupancy": args.occupancy, "occupancy_sigma": args.occupancy_sigma,
+                         "occupancy_cells_set": round(rend.occupancy.live_fraction(), 4),
+                         "live_samples_fraction": round(live_samples / (args.frames * n * (2 * args.n_coarse
+                                                                                          + args.n_fine)), 4)})
+        print(json.dumps(line), flush=True)
     if dist is not None:
         dist.destroy_process_group()
 

@@ -132,6 +132,35 @@ class VolumeRenderer(nn.Module):
         # (inference only; rgb changes by <= T_stop).
         self.t_stop = None
         self.last_fine_samples = 0
+        # Empty-space skipping (avr.occupancy; not in the reference): None = evaluate every sample; an
+        # OccupancyGrid, or a list with one grid per scene, evaluates the field only where the grid is live and
+        # hands the composite exact zeros elsewhere (inference on the fused single-view path, eager only).
+        self.occupancy = None
+        self.last_live_samples = 0          # field samples evaluated by the last gated call, both passes
+        self.last_live_by_pass = (0, 0)     # (coarse, fine)
+
+    def _occupancy_grids(self, SB, radiance_field, fuse, dev):
+        """The per-scene grids of a gated call, or ValueError where gating does not apply: never a quiet fallback
+        to the ungated render."""
+        occ = self.occupancy
+        grids = list(occ) if isinstance(occ, (list, tuple)) else [occ]
+        if torch.is_grad_enabled():
+            raise ValueError("VolumeRenderer.occupancy is inference only: call under torch.no_grad()")
+        if self.t_stop is not None:
+            raise ValueError("VolumeRenderer.occupancy cannot be combined with t_stop")
+        if len(grids) != SB:
+            raise ValueError(f"VolumeRenderer.occupancy holds {len(grids)} grid(s) for {SB} scene(s)")
+        if self.n_coarse + self.n_fine > _lib.OCC_MAX_SAMPLES:
+            raise ValueError(f"VolumeRenderer.occupancy takes at most {_lib.OCC_MAX_SAMPLES} samples per ray")
+        if not fuse:
+            raise ValueError("VolumeRenderer.occupancy needs a net on the single-view fused path")
+        if any(g.stale(radiance_field) for g in grids):
+            raise ValueError("VolumeRenderer.occupancy: a grid was built from parameters, a latent map or source "
+                             "views that have changed since; rebuild it (OccupancyGrid.from_field)")
+        if dev.type == "cuda" and torch.cuda.is_current_stream_capturing():
+            raise ValueError("VolumeRenderer.occupancy reads the live count back to the host: it cannot be captured "
+                             "in a graph")
+        return grids
 
     @classmethod
     def from_conf(cls, conf, white_back=True):
@@ -186,6 +215,8 @@ class VolumeRenderer(nn.Module):
         near, far = float(self.near[0]), float(self.far[0])
         nf = self.n_fine - self.n_fine_depth
         Nc, Nt = self.n_coarse, self.n_coarse + self.n_fine
+        fuse = hasattr(radiance_field, "can_fuse") and radiance_field.can_fuse(x_pix)
+        grids = None if self.occupancy is None else self._occupancy_grids(SB, radiance_field, fuse, dev)
         draws = self._draws(SB, R, dev, noise)
         seed, off = (self.seed or 0), self._offset
         ids = None
@@ -202,11 +233,19 @@ class VolumeRenderer(nn.Module):
             x_pix, intrinsics, cam2world, near, far, Nc, noise=None if draws is None else draws["coarse"], seed=seed,
             offset=off, ray_ids=ids, want_depth_row=fast_depth)
 
-        fuse = hasattr(radiance_field, "can_fuse") and radiance_field.can_fuse(x_pix)
         self.last_path = "fused" if fuse else "module"
+        live = []
 
         def field(z, coarse):
             n = z.shape[-1]
+            if grids is not None:   # per scene: the field on the live samples only, exact zeros elsewhere
+                from .occupancy import gated_field
+                fusedf = radiance_field.fused()
+                outs = [gated_field(fusedf, grids[b], ro[b], rd[b], z[b * R:(b + 1) * R], coarse, sb=b)
+                        for b in range(SB)]
+                live.append(sum(m for _, m in outs))
+                out = outs[0][0] if SB == 1 else torch.cat([f for f, _ in outs], 0)
+                return out.reshape(SB * R, n, 4)
             if fuse:
                 fusedf = radiance_field.fused()
                 if SB == 1:
@@ -227,6 +266,8 @@ class VolumeRenderer(nn.Module):
         else:
             ff = field(z_sorted, False)
             self.last_fine_samples = z_sorted.numel()
+            if grids is not None:
+                self.last_live_by_pass, self.last_live_samples = tuple(live), sum(live)
             if fast_depth:
                 # the fine weights are not returned (renderers.py:264-277): no store without autograd
                 rgb_f, dist_f, _, depth = ops.composite_depth(z_sorted, ff, ro, rd, depth_row, self.white_back)

@@ -63,20 +63,33 @@ def to_uint8(img):
 
 
 def render_orbit(renderer, radiance_field, intrinsics, num_frames, radius, height, width=None, fine=True,
-                 device=None, t_stop=None, on_frame=None):
+                 device=None, t_stop=None, on_frame=None, occupancy=None, occupancy_sigma=0.0, occupancy_box=1.0):
     """Render num_frames full frames around the orbit with `renderer`
     (e.g. avr.renderers.VolumeRenderer) and a ready radiance field. One
     renderer call per frame (all H * W rays at once), no_grad. Returns
     (frames, stats): frames uint8 (H, W, 3); stats = seconds, rays/s and the
-    fine samples evaluated (< H * W * (n_coarse + n_fine) once rays terminate)."""
+    fine samples evaluated (< H * W * (n_coarse + n_fine) once rays terminate).
+    occupancy = RES (the CLI's --occupancy / --occupancy-sigma): a RES^3 grid over
+    [-occupancy_box, occupancy_box]^3 is built from the field once before the frames
+    (avr.occupancy.OccupancyGrid.from_field) and gates every frame; stats then carry
+    the live share of the field samples, which is printed at the end."""
     width = width or height
     device = device or intrinsics.device
     K = intrinsics.reshape(1, 3, 3).to(device)
     x_pix = get_opencv_pixel_coordinates(height, width).reshape(1, -1, 2).to(device)
     n = x_pix.shape[1]
+    grid = None
+    if occupancy is not None:
+        from .occupancy import OccupancyGrid
+        h = float(occupancy_box)
+        grid = OccupancyGrid.from_field(radiance_field, (-h, -h, -h), (h, h, h), (int(occupancy),) * 3,
+                                        sigma_thr=occupancy_sigma)
     prev = getattr(renderer, "t_stop", None)
+    prev_occ = getattr(renderer, "occupancy", None)
     renderer.t_stop = t_stop
-    frames, fine_samples = [], 0
+    if grid is not None:
+        renderer.occupancy = grid
+    frames, fine_samples, live_samples = [], 0, 0
     try:
         torch.cuda.synchronize(device)
         t0 = time.perf_counter()
@@ -85,6 +98,7 @@ def render_orbit(renderer, radiance_field, intrinsics, num_frames, radius, heigh
                 c2w = c2w.to(device).reshape(1, 1, 4, 4).expand(1, n, 4, 4)
                 rgb_c, rgb_f, _, _ = renderer(c2w, K, x_pix, radiance_field)
                 fine_samples += getattr(renderer, "last_fine_samples", 0)
+                live_samples += getattr(renderer, "last_live_samples", 0)
                 img = (rgb_f if fine else rgb_c)[0].reshape(height, width, 3)
                 frame = to_uint8(img.float().cpu().numpy())
                 frames.append(frame)
@@ -94,8 +108,15 @@ def render_orbit(renderer, radiance_field, intrinsics, num_frames, radius, heigh
         secs = time.perf_counter() - t0
     finally:
         renderer.t_stop = prev
-    return frames, {"seconds": secs, "rays_per_s": num_frames * n / secs, "frames": num_frames,
-                    "rays_per_frame": n, "fine_samples": fine_samples}
+        if grid is not None:
+            renderer.occupancy = prev_occ
+    stats = {"seconds": secs, "rays_per_s": num_frames * n / secs, "frames": num_frames,
+             "rays_per_frame": n, "fine_samples": fine_samples}
+    if grid is not None:
+        per_ray = 2 * renderer.n_coarse + renderer.n_fine    # the coarse pass, then coarse + fine positions again
+        stats["live_share"] = live_samples / max(num_frames * n * per_ray, 1)
+        print(f"occupancy {occupancy}^3: {stats['live_share']:.4f} of the field samples were live")
+    return frames, stats
 
 
 def generate_video(model_input, num_frames, radius, net, model, fine=True):

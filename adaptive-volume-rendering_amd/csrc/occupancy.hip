@@ -1,0 +1,227 @@
+// Occupancy-grid empty-space skipping for VolumeRenderer inference (not in the reference; DESIGN.md "Occupancy
+// grid"): a per-scene bit grid over an axis-aligned box, a per-sample live test against it, and the compaction /
+// expansion around one avr_field_fwd_points launch on the live samples.
+//
+//   avr_occ_build     sigma planes -> bits          one lane per cell, 64 cells = one ballot = two bit words
+//   avr_occ_classify  (ro, rd, z)  -> mask, counts  one wave per ray, one lane per sample, one ballot per 64 samples
+//   avr_occ_compact   mask, offsets -> xyz, viewdirs of the live samples, ray-major sample order
+//   avr_occ_expand    field of the live samples -> the dense (R*N, 4) field, zeros for dead samples
+//
+// A live sample's rank in the compacted list is offsets[ray] + popcount of the lower mask bits of its ray: no slot
+// array, no atomics, no data-dependent order, so every output is bit-reproducible. The point is formed with the
+// operations of field_common.h's sample_geom (fadd(ro, fmul(rd, z))), so a compacted point is the point
+// avr_field_fwd_rays would have formed, bit for bit. All four are bandwidth-trivial next to the field kernel; the
+// grid (at most 2 Mbit) stays in L2.
+#include "avr_common.h"
+
+namespace avr {
+
+constexpr int kOccThreads = 256;
+constexpr int kOccRaysPerBlock = kOccThreads / kWave;
+
+struct OccGrid {
+  float lo[3], inv[3];
+  int res[3];
+  const uint32_t* bits;
+};
+
+// The live test of include/avr.h: the float comparisons 0 <= t < res are the integer test on floorf(t) for every
+// finite t and stay defined for an infinite one (a finite point far outside the box: dead).
+__device__ __forceinline__ bool occ_live(const OccGrid& g, float p0, float p1, float p2) {
+  if (!(isfinite(p0) && isfinite(p1) && isfinite(p2))) return true;   // the field sees it, as in the ungated render
+  const float t0 = fmul(fsub(p0, g.lo[0]), g.inv[0]);
+  const float t1 = fmul(fsub(p1, g.lo[1]), g.inv[1]);
+  const float t2 = fmul(fsub(p2, g.lo[2]), g.inv[2]);
+  if (!(t0 >= 0.f && t0 < (float)g.res[0] && t1 >= 0.f && t1 < (float)g.res[1] && t2 >= 0.f && t2 < (float)g.res[2]))
+    return false;
+  const int ix = (int)floorf(t0), iy = (int)floorf(t1), iz = (int)floorf(t2);
+  const int word = (iz * g.res[1] + iy) * (g.res[0] >> 5) + (ix >> 5);
+  return (g.bits[word] >> (ix & 31)) & 1u;
+}
+
+__device__ __forceinline__ int lane_rank(uint64_t m, int lane) { return __popcll(m & ((1ull << lane) - 1ull)); }
+
+__global__ void __launch_bounds__(kOccThreads) occ_build_kernel(const float* __restrict__ sigma, int n_planes, int rx,
+                                                                 int ry, int rz, float thr, int dilate,
+                                                                 uint32_t* __restrict__ bits) {
+  const int n_cells = rx * ry * rz;   // <= 2^24
+  const int cell = blockIdx.x * kOccThreads + threadIdx.x;
+  bool occ = false;
+  if (cell < n_cells) {
+    const int ix = cell % rx, iy = (cell / rx) % ry, iz = cell / (rx * ry);
+    const int x0 = max(ix - dilate, 0), x1 = min(ix + dilate, rx - 1);
+    const int y0 = max(iy - dilate, 0), y1 = min(iy + dilate, ry - 1);
+    const int z0 = max(iz - dilate, 0), z1 = min(iz + dilate, rz - 1);
+    for (int k = 0; k < n_planes && !occ; ++k) {
+      const float* plane = sigma + (int64_t)k * n_cells;
+      for (int z = z0; z <= z1; ++z)
+        for (int y = y0; y <= y1; ++y)
+          for (int x = x0; x <= x1; ++x) occ |= !(plane[(z * ry + y) * rx + x] <= thr);   // NaN: occupied
+    }
+  }
+  const uint64_t m = __ballot(occ);   // cells 64 * wave .. + 63: words 2 * wave and 2 * wave + 1 (rx % 32 == 0)
+  const int lane = threadIdx.x & (kWave - 1);
+  if ((lane == 0 || lane == 32) && cell < n_cells) bits[cell >> 5] = (uint32_t)(m >> lane);
+}
+
+__global__ void __launch_bounds__(kOccThreads) occ_classify_kernel(OccGrid g, const float* __restrict__ ro,
+                                                                    const float* __restrict__ rd,
+                                                                    const float* __restrict__ z, int64_t n_rays,
+                                                                    int n_samples, uint64_t* __restrict__ mask,
+                                                                    int32_t* __restrict__ counts) {
+  const int64_t r = (int64_t)blockIdx.x * kOccRaysPerBlock + (threadIdx.x >> 6);
+  if (r >= n_rays) return;   // whole waves leave together
+  const int lane = threadIdx.x & (kWave - 1);
+  const int n_words = (n_samples + kWave - 1) / kWave;
+  const float o0 = ro[3 * r], o1 = ro[3 * r + 1], o2 = ro[3 * r + 2];
+  const float d0 = rd[3 * r], d1 = rd[3 * r + 1], d2 = rd[3 * r + 2];
+  int count = 0;
+  for (int w = 0; w < n_words; ++w) {
+    const int s = w * kWave + lane;
+    bool live = false;
+    if (s < n_samples) {
+      const float zz = z[r * n_samples + s];
+      live = occ_live(g, fadd(o0, fmul(d0, zz)), fadd(o1, fmul(d1, zz)), fadd(o2, fmul(d2, zz)));
+    }
+    const uint64_t m = __ballot(live);
+    if (lane == 0) mask[r * n_words + w] = m;
+    count += __popcll(m);
+  }
+  if (lane == 0) counts[r] = count;
+}
+
+__global__ void __launch_bounds__(kOccThreads) occ_compact_kernel(const float* __restrict__ ro,
+                                                                   const float* __restrict__ rd,
+                                                                   const float* __restrict__ z,
+                                                                   const uint64_t* __restrict__ mask,
+                                                                   const int64_t* __restrict__ offsets, int64_t n_rays,
+                                                                   int n_samples, int64_t n_live,
+                                                                   float* __restrict__ xyz, float* __restrict__ vd) {
+  const int64_t r = (int64_t)blockIdx.x * kOccRaysPerBlock + (threadIdx.x >> 6);
+  if (r >= n_rays) return;
+  const int lane = threadIdx.x & (kWave - 1);
+  const int n_words = (n_samples + kWave - 1) / kWave;
+  const float o0 = ro[3 * r], o1 = ro[3 * r + 1], o2 = ro[3 * r + 2];
+  const float d0 = rd[3 * r], d1 = rd[3 * r + 1], d2 = rd[3 * r + 2];
+  int64_t base = offsets[r];
+  for (int w = 0; w < n_words; ++w) {
+    const uint64_t m = mask[r * n_words + w];
+    const int s = w * kWave + lane;
+    const int64_t q = base + lane_rank(m, lane);
+    // s < n_samples and 0 <= q < n_live hold for the mask and offsets of avr_occ_classify; checked so that
+    // inconsistent arguments cannot write outside xyz / viewdirs
+    if (((m >> lane) & 1ull) && s < n_samples && q >= 0 && q < n_live) {
+      const float zz = z[r * n_samples + s];
+      xyz[3 * q] = fadd(o0, fmul(d0, zz));
+      xyz[3 * q + 1] = fadd(o1, fmul(d1, zz));
+      xyz[3 * q + 2] = fadd(o2, fmul(d2, zz));
+      vd[3 * q] = d0; vd[3 * q + 1] = d1; vd[3 * q + 2] = d2;
+    }
+    base += __popcll(m);
+  }
+}
+
+__global__ void __launch_bounds__(kOccThreads) occ_expand_kernel(const floatx4* __restrict__ field_c,
+                                                                  const uint64_t* __restrict__ mask,
+                                                                  const int64_t* __restrict__ offsets, int64_t n_rays,
+                                                                  int n_samples, int64_t n_live,
+                                                                  floatx4* __restrict__ field) {
+  const int64_t r = (int64_t)blockIdx.x * kOccRaysPerBlock + (threadIdx.x >> 6);
+  if (r >= n_rays) return;
+  const int lane = threadIdx.x & (kWave - 1);
+  const int n_words = (n_samples + kWave - 1) / kWave;
+  int64_t base = n_live > 0 ? offsets[r] : 0;
+  for (int w = 0; w < n_words; ++w) {
+    const uint64_t m = n_live > 0 ? mask[r * n_words + w] : 0ull;
+    const int s = w * kWave + lane;
+    const int64_t q = base + lane_rank(m, lane);
+    floatx4 v = {0.f, 0.f, 0.f, 0.f};
+    if (((m >> lane) & 1ull) && q >= 0 && q < n_live) v = field_c[q];   // (the range check: as in occ_compact_kernel)
+    if (s < n_samples) field[r * n_samples + s] = v;
+    base += __popcll(m);
+  }
+}
+
+}  // namespace avr
+
+using namespace avr;
+
+static int occ_rays(const char* who, int64_t n_rays, int n_samples, int64_t* blocks) {
+  AVR_REQUIRE(n_rays >= 0, "%s: negative n_rays", who);
+  AVR_REQUIRE(n_samples >= 1 && n_samples <= AVR_OCC_MAX_SAMPLES, "%s: n_samples %d outside 1..%d", who, n_samples,
+              AVR_OCC_MAX_SAMPLES);
+  *blocks = (n_rays + kOccRaysPerBlock - 1) / kOccRaysPerBlock;
+  AVR_REQUIRE(*blocks < (1ll << 31), "%s: too many rays", who);
+  return AVR_OK;
+}
+
+static int occ_res(const char* who, const int* res) {
+  AVR_REQUIRE(res, "%s: null res", who);
+  for (int a = 0; a < 3; ++a)
+    AVR_REQUIRE(res[a] >= 1 && res[a] <= AVR_OCC_MAX_RES, "%s: res[%d] = %d outside 1..%d", who, a, res[a],
+                AVR_OCC_MAX_RES);
+  AVR_REQUIRE(res[0] % 32 == 0, "%s: res[0] = %d is not a multiple of 32", who, res[0]);
+  return AVR_OK;
+}
+
+extern "C" int avr_occ_build(const float* sigma, int n_planes, const int* res, float thr, int dilate, uint32_t* bits,
+                             void* stream) {
+  int rc = occ_res("avr_occ_build", res);
+  if (rc) return rc;
+  AVR_REQUIRE(n_planes >= 1, "avr_occ_build: n_planes %d below 1", n_planes);
+  AVR_REQUIRE(dilate >= 0 && dilate <= 2, "avr_occ_build: dilate %d outside 0..2", dilate);
+  AVR_REQUIRE(sigma && bits, "avr_occ_build: null pointer");
+  const int n_cells = res[0] * res[1] * res[2];
+  occ_build_kernel<<<(unsigned)((n_cells + kOccThreads - 1) / kOccThreads), kOccThreads, 0, as_stream(stream)>>>(
+      sigma, n_planes, res[0], res[1], res[2], thr, dilate, bits);
+  return check_launch("occ_build_kernel");
+}
+
+extern "C" int avr_occ_classify(const avr_occ_grid* grid, const float* ro, const float* rd, const float* z,
+                                int64_t n_rays, int n_samples, uint64_t* mask, int32_t* counts, void* stream) {
+  AVR_REQUIRE(grid, "avr_occ_classify: null grid");
+  int64_t blocks;
+  int rc = occ_res("avr_occ_classify", grid->res);
+  if (rc || (rc = occ_rays("avr_occ_classify", n_rays, n_samples, &blocks))) return rc;
+  AVR_REQUIRE(grid->bits, "avr_occ_classify: null grid bits");
+  if (n_rays == 0) return AVR_OK;
+  AVR_REQUIRE(ro && rd && z && mask && counts, "avr_occ_classify: null pointer");
+  OccGrid g;
+  for (int a = 0; a < 3; ++a) { g.lo[a] = grid->lo[a]; g.inv[a] = grid->inv[a]; g.res[a] = grid->res[a]; }
+  g.bits = grid->bits;
+  occ_classify_kernel<<<(unsigned)blocks, kOccThreads, 0, as_stream(stream)>>>(g, ro, rd, z, n_rays, n_samples, mask,
+                                                                              counts);
+  return check_launch("occ_classify_kernel");
+}
+
+extern "C" int avr_occ_compact(const float* ro, const float* rd, const float* z, const uint64_t* mask,
+                               const int64_t* offsets, int64_t n_rays, int n_samples, int64_t n_live, float* xyz,
+                               float* viewdirs, void* stream) {
+  int64_t blocks;
+  int rc = occ_rays("avr_occ_compact", n_rays, n_samples, &blocks);
+  if (rc) return rc;
+  AVR_REQUIRE(n_live >= 0 && n_live <= n_rays * n_samples, "avr_occ_compact: n_live %lld outside 0..n_rays * n_samples",
+              (long long)n_live);
+  if (n_rays == 0 || n_live == 0) return AVR_OK;
+  AVR_REQUIRE(ro && rd && z && mask && offsets && xyz && viewdirs, "avr_occ_compact: null pointer");
+  occ_compact_kernel<<<(unsigned)blocks, kOccThreads, 0, as_stream(stream)>>>(ro, rd, z, mask, offsets, n_rays,
+                                                                             n_samples, n_live, xyz, viewdirs);
+  return check_launch("occ_compact_kernel");
+}
+
+extern "C" int avr_occ_expand(const float* field_c, const uint64_t* mask, const int64_t* offsets, int64_t n_rays,
+                              int n_samples, int64_t n_live, float* field, void* stream) {
+  int64_t blocks;
+  int rc = occ_rays("avr_occ_expand", n_rays, n_samples, &blocks);
+  if (rc) return rc;
+  AVR_REQUIRE(n_live >= 0 && n_live <= n_rays * n_samples, "avr_occ_expand: n_live %lld outside 0..n_rays * n_samples",
+              (long long)n_live);
+  if (n_rays == 0) return AVR_OK;
+  AVR_REQUIRE(field, "avr_occ_expand: null field");
+  AVR_REQUIRE(n_live == 0 || (field_c && mask && offsets), "avr_occ_expand: null pointer with n_live > 0");
+  AVR_REQUIRE((((uintptr_t)field | (uintptr_t)field_c) & 15) == 0, "avr_occ_expand: field rows must be 16-B aligned");
+  occ_expand_kernel<<<(unsigned)blocks, kOccThreads, 0, as_stream(stream)>>>(
+      reinterpret_cast<const floatx4*>(field_c), mask, offsets, n_rays, n_samples, n_live,
+      reinterpret_cast<floatx4*>(field));
+  return check_launch("occ_expand_kernel");
+}

@@ -680,6 +680,50 @@ typedef struct {
 int avr_adam_step(const avr_adam_tensor* tensors, int64_t n_tensors, double lr, double beta1, double beta2, double eps,
                   double weight_decay, float* step, void* stream);
 
+/* ---------------------------------------------------------- occupancy grid
+ * Additions within ABI 18 (no version change): empty-space skipping for VolumeRenderer inference (not in the
+ * reference; DESIGN.md "Occupancy grid"). A grid is a bit per cell of an axis-aligned box [lo, hi) with res =
+ * (rx, ry, rz) cells, each in 1 .. AVR_OCC_MAX_RES, rx a multiple of 32, packed along x into uint32 words: cell
+ * (ix, iy, iz) is bit ix % 32 of word (iz * ry + iy) * (rx / 32) + ix / 32. inv[a] = (float)(res[a] / ((double)hi[a]
+ * - (double)lo[a])) is computed by the caller.
+ * A sample (ray r, z[r, s]) is the point p = fadd(ro, fmul(rd, z)) of avr_field_fwd_rays (the same two roundings,
+ * uncontracted); with t[a] = fmul(fsub(p[a], lo[a]), inv[a]) and i[a] = (int)floorf(t[a]) it is LIVE iff every
+ * 0 <= i[a] < res[a] (tested as 0 <= t[a] < res[a], the same for finite t and defined for an infinite one) and the
+ * cell's bit is set. A point outside the box is dead; a point with a non-finite coordinate is live (the field sees
+ * it, as in the ungated render).
+ *   avr_occ_build: sigma (n_planes, rz, ry, rx) fp32 -> bits (rx / 32 * ry * rz words, every word written): a cell
+ *     is set iff any plane at any cell within Chebyshev distance dilate (0, 1 or 2; neighbours clamped at the box
+ *     faces) has !(sigma <= thr) -- NaN counts as occupied.
+ *   avr_occ_classify: ro, rd (n_rays, 3), z (n_rays, n_samples), n_samples in 1 .. AVR_OCC_MAX_SAMPLES -> mask
+ *     (n_rays, ceil(n_samples / 64)) uint64, bit s % 64 of word s / 64 = sample s is live (bits past n_samples
+ *     clear), and counts (n_rays) int32 = live samples of the ray.
+ *   avr_occ_compact: mask and offsets (n_rays) int64 = the exclusive prefix sum of counts -> xyz, viewdirs
+ *     (n_live, 3): the live samples' points and ray directions in ray-major sample order (rank of a live sample =
+ *     offsets[r] + popcount of the lower mask bits of its ray), n_live = the sum of counts.
+ *   avr_occ_expand: field_c (n_live, 4) = the field at the compacted points -> field (n_rays * n_samples, 4): a
+ *     live sample's row of field_c, exactly 0.0f in all four channels for a dead one; every element is written (no
+ *     memset). field and field_c 16-B aligned.
+ * No atomics, so every output is bit-reproducible. Checked before any HIP call (AVR_E_INVALID): null pointers, res
+ * and n_samples out of range, rx % 32 != 0, dilate outside 0 .. 2, n_planes < 1, negative n_rays, n_live outside
+ * 0 .. n_rays * n_samples. n_rays == 0 launches nothing and succeeds, as does compact with n_live == 0; expand with
+ * n_live == 0 writes zeros and reads neither field_c, mask nor offsets (they may be NULL).                        */
+#define AVR_OCC_MAX_RES 256
+#define AVR_OCC_MAX_SAMPLES 256
+typedef struct {
+  float lo[3];
+  float inv[3];
+  int res[3];             /* rx, ry, rz */
+  const uint32_t* bits;   /* device */
+} avr_occ_grid;
+int avr_occ_build(const float* sigma, int n_planes, const int* res, float thr, int dilate, uint32_t* bits,
+                  void* stream);
+int avr_occ_classify(const avr_occ_grid* grid, const float* ro, const float* rd, const float* z, int64_t n_rays,
+                     int n_samples, uint64_t* mask, int32_t* counts, void* stream);
+int avr_occ_compact(const float* ro, const float* rd, const float* z, const uint64_t* mask, const int64_t* offsets,
+                    int64_t n_rays, int n_samples, int64_t n_live, float* xyz, float* viewdirs, void* stream);
+int avr_occ_expand(const float* field_c, const uint64_t* mask, const int64_t* offsets, int64_t n_rays, int n_samples,
+                   int64_t n_live, float* field, void* stream);
+
 /* ------------------------------------------------------------ measurement
  * Streaming device copy dst[0, n_bytes) = src[0, n_bytes) (16-B aligned,
  * n_bytes a multiple of 16): the achievable-HBM yardstick bench.py reports
