@@ -107,6 +107,7 @@ class AdamTensor(ctypes.Structure):
 
 OCC_MAX_RES = 256       # avr.h AVR_OCC_MAX_RES: cells per axis of an occupancy grid
 OCC_MAX_SAMPLES = 256   # avr.h AVR_OCC_MAX_SAMPLES: samples per ray of avr_occ_classify / _compact / _expand
+OCC_SCAN_RAYS = 2048    # avr.h AVR_OCC_SCAN_RAYS: rays one workgroup of avr_occ_scan owns
 
 
 class OccGrid(ctypes.Structure):
@@ -215,6 +216,12 @@ _SIGS = {
     "avr_occ_compact": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, i64, c_int, i64, c_void_p, c_void_p,
                         c_void_p],
     "avr_occ_expand": [c_void_p, c_void_p, c_void_p, i64, c_int, i64, c_void_p, c_void_p],
+    "avr_occ_scan": [c_void_p, i64, c_void_p, c_void_p, c_void_p],
+    "avr_occ_compact_counted": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, i64, c_int, c_void_p, i64, c_void_p,
+                                c_void_p, c_void_p],
+    "avr_occ_expand_counted": [c_void_p, c_void_p, c_void_p, i64, c_int, c_void_p, i64, c_void_p, c_void_p],
+    "avr_field_fwd_points_counted": [ctypes.POINTER(FieldDims), ctypes.POINTER(ViewDesc), c_void_p, c_void_p,
+                                     c_void_p, c_void_p, i64, c_void_p, c_void_p, c_void_p],
     "avr_stream_copy": [c_void_p, c_void_p, i64, c_void_p],
     "avr_stream_fill": [c_void_p, i64, c_uint32, c_void_p],
 }

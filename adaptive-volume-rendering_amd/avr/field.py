@@ -518,6 +518,32 @@ class FusedField:
              ptr(table), ptr(p), ptr(v), M, ptr(out), stream_of(p))
         return out
 
+    def forward_points_scene_counted(self, xyz, viewdirs, n_points, coarse, sb=0, out=None):
+        """forward_points_scene over the first n_points rows of xyz, viewdirs (capacity, 3), n_points a 0-dim int64
+        tensor on the device (avr_field_fwd_points_counted): rows at or beyond it are neither read nor written, no
+        host read sizes the launch. -> (capacity, 4). ReLU nets without BatchNorm or use_spade: the other inference
+        variants have no counted kernel and raise ValueError (never another path)."""
+        cap = xyz.shape[0]
+        if xyz.dtype != F32 or viewdirs.dtype != F32 or not (xyz.is_contiguous() and viewdirs.is_contiguous()):
+            raise ValueError("forward_points_scene_counted: xyz and viewdirs must be contiguous fp32 (a conversion "
+                             "would read the rows beyond the count)")
+        if n_points.dtype != torch.int64 or n_points.numel() != 1:
+            raise ValueError("forward_points_scene_counted: n_points must be one int64 on the device")
+        require_device(xyz, viewdirs)
+        if not n_points.is_cuda:
+            raise ValueError("forward_points_scene_counted: n_points must be on the device")
+        entry = self.packed(coarse)
+        dims = entry.dims_as(PRECISIONS[self.precision])
+        if dims.bn or dims.spade or dims.beta > 0:
+            raise ValueError("device-count occupancy gating (occupancy_count = 'device') has counted field kernels "
+                             "for ReLU nets without BatchNorm or use_spade only; use occupancy_count = 'host'")
+        if out is None:
+            out = torch.empty(cap, 4, device=xyz.device, dtype=F32)
+        table = self.table(coarse, sb)
+        call("avr_field_fwd_points_counted", ctypes.byref(dims), ctypes.byref(self.view(sb)), ptr(entry.packed),
+             ptr(table), ptr(xyz), ptr(viewdirs), cap, ptr(n_points), ptr(out), stream_of(xyz))
+        return out
+
     # ----------------------------------------------------------- training
     def forward_train(self, xyz, viewdirs, coarse):
         """The rf(xyz, viewdirs, coarse) protocol with autograd: HIP forward that

@@ -23,6 +23,14 @@ net.field_precision captures again too. The packed weights and lin_z tables the 
 referenced by the GraphedRenderer, so an eager call that replaces those cache entries (another scene count or
 precision) cannot free memory a replay reads. Replacing a Parameter object itself is not seen: call refresh()
 after that. Warm-ups and re-captures leave the renderer's Philox offset where it was.
+
+Occupancy gating: a renderer with `occupancy` set is accepted when `renderer.occupancy_count == "device"` (the live
+count stays on the device and is read by the captured kernels at replay time; the host-read mode is refused). The
+captured classify launches read the grids' bits through their addresses, which the GraphedRenderer holds:
+`grid.copy_(new_grid)` swaps a grid in without a new capture, and `renderer.last_live_counts` holds the replay's
+live counts. The graph's pool keeps the worst-case compacted buffers (40 B per sample) for as long as the graph
+lives. A re-capture caused by a weight change meets the renderer's stale-grid ValueError, as an eager call would:
+rebuild the grid (OccupancyGrid.from_field), assign it to renderer.occupancy, then call refresh().
 """
 import torch
 
@@ -49,9 +57,10 @@ class GraphedRenderer:
     def __init__(self, renderer, net, cam2world, intrinsics, x_pix, warmup=2):
         if renderer.t_stop is not None:
             raise ValueError("GraphedRenderer: early termination sizes its launches on the host (t_stop must be None)")
-        if getattr(renderer, "occupancy", None) is not None:
+        if getattr(renderer, "occupancy", None) is not None and \
+                getattr(renderer, "occupancy_count", "host") != "device":
             raise ValueError("GraphedRenderer: occupancy gating reads the live count back to the host "
-                             "(renderer.occupancy must be None)")
+                             "(renderer.occupancy must be None, or renderer.occupancy_count 'device')")
         if hasattr(renderer, "stage_host_draws") and renderer.seed is None:
             raise ValueError("GraphedRenderer: the adaptive renderers draw their start distances on the host "
                              "unless seeded (set renderer.seed)")
@@ -117,6 +126,11 @@ class GraphedRenderer:
         self._held_buffers = fused.cache_tensors() if fused is not None else []
         if hasattr(renderer, "cache_tensors"):   # the adaptive renderers' gate tables
             self._held_buffers = self._held_buffers + renderer.cache_tensors()
+        # the occupancy grids' bits the captured classify launches read (occupancy_count = "device"): held like the
+        # buffers above; OccupancyGrid.copy_ refills them in place between replays
+        occ = getattr(renderer, "occupancy", None)
+        self._held_occupancy = [g.bits for g in (occ if isinstance(occ, (list, tuple)) else [occ])] \
+            if occ is not None else []
         self._held_precision = getattr(net, "field_precision", None)
         views = self._views()
         self._held_views = views

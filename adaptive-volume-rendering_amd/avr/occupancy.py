@@ -8,8 +8,16 @@ grid", include/avr.h "occupancy grid").
 A grid is a bit per cell of an axis-aligned box. A sample whose point falls in a clear cell, or outside the box, is
 not evaluated: the composite sees exactly 0.0 in all four channels for it (sigma = 0). The live samples are compacted
 in ray-major sample order, evaluated by one avr_field_fwd_points launch and scattered back (gated_field): classify
--> cumsum -> one host read of the live count -> compact -> field -> expand. The host read makes the path eager only:
+-> cumsum -> one host read of the live count -> compact -> field -> expand. The host read makes that path eager only:
 it cannot be recorded in a HIP-graph capture.
+
+    renderer.occupancy_count = "device"           # "host" (default): the chain above
+
+keeps the live count on the device instead (gated_field(count="device")): classify -> avr_occ_scan ->
+avr_occ_compact_counted -> avr_field_fwd_points_counted -> avr_occ_expand_counted, no host read and no torch kernel,
+so the gated frame can be captured (avr.graphs.GraphedRenderer) and OccupancyGrid.copy_ gives a captured graph a
+new grid without a new capture. Its price is memory: the compacted buffers are sized for the worst case, R * N rows
+(40 B per sample), where the host-read path allocates the live share only.
 
 What the render loses is what the grid calls empty. from_field marks a cell from sigma at its centre alone, for a
 handful of view directions, so a density feature thinner than a cell, or one that only other view directions see, can
@@ -79,6 +87,18 @@ class OccupancyGrid:
     @property
     def device(self):
         return self.bits.device
+
+    def copy_(self, other):
+        """This grid's bits, key and kept tensors become `other`'s, in place (same box and resolution, else
+        ValueError): the bits tensor keeps its address, so a captured graph that reads it (GraphedRenderer with
+        occupancy_count = "device") renders with the new grid from its next replay on, without a new capture. The
+        copy is ordered on the current stream."""
+        if other.res != self.res or other.lo != self.lo or other.hi != self.hi:
+            raise ValueError(f"OccupancyGrid.copy_: box {other.lo} .. {other.hi} res {other.res} into box {self.lo} "
+                             f".. {self.hi} res {self.res}: the box and the resolution must match")
+        self.bits.copy_(other.bits)
+        self.key, self._keep = other.key, other._keep
+        return self
 
     def live_fraction(self):
         """Share of the cells whose bit is set (a host read of the bits)."""
@@ -182,10 +202,48 @@ def expand(field_c, mask, offsets, R, N, n_live):
     return field
 
 
-def gated_field(fused, grid, ro, rd, z, coarse, sb=0):
-    """The field of scene `sb` at ro[r] + rd[r] * z[r, s] where `grid` is live, exactly zero elsewhere:
-    (field (R * N, 4), n_live). One host read (the live count); no field launch when nothing is live."""
+def scan(counts, total=None):
+    """avr_occ_scan: counts (R,) int32 -> offsets (R,) int64 (exclusive prefix sums), total 0-dim int64 on the
+    device (written into `total` when given)."""
+    R = counts.shape[0]
+    require_device(counts)
+    offsets = torch.empty(R, device=counts.device, dtype=torch.int64)
+    if total is None:
+        total = torch.empty((), device=counts.device, dtype=torch.int64)
+    call("avr_occ_scan", ptr(counts), R, ptr(offsets), ptr(total), stream_of(counts))
+    return offsets, total
+
+
+def _gated_field_device(fused, grid, ro, rd, z, coarse, sb, total):
+    """gated_field with the live count on the device: every buffer is sized for the worst case (capacity R * N), no
+    host read, no torch kernel (torch.empty only), legal on a capturing stream."""
     R, N = z.shape
+    cap = R * N
+    mask, counts = classify(grid, ro, rd, z)
+    offsets, total = scan(counts, total)
+    xyz = torch.empty(cap, 3, device=z.device, dtype=F32)
+    vd = torch.empty_like(xyz)
+    call("avr_occ_compact_counted", ptr(ro), ptr(rd), ptr(z), ptr(mask), ptr(offsets), R, N, ptr(total), cap,
+         ptr(xyz), ptr(vd), stream_of(z))
+    field_c = fused.forward_points_scene_counted(xyz, vd, total, coarse, sb)
+    field = torch.empty(cap, 4, device=z.device, dtype=F32)
+    call("avr_occ_expand_counted", ptr(field_c), ptr(mask), ptr(offsets), R, N, ptr(total), cap, ptr(field),
+         stream_of(z))
+    return field, total
+
+
+def gated_field(fused, grid, ro, rd, z, coarse, sb=0, count="host", total=None):
+    """The field of scene `sb` at ro[r] + rd[r] * z[r, s] where `grid` is live, exactly zero elsewhere:
+    (field (R * N, 4), n_live). count="host": one host read (the live count, an int); no field launch when nothing
+    is live. count="device": the count stays on the device (a 0-dim int64 tensor, `total` when given), nothing is
+    read back and the call may be captured."""
+    if count not in ("host", "device"):
+        raise ValueError(f"gated_field: count must be 'host' or 'device', got {count!r}")
+    R, N = z.shape
+    if count == "device":
+        ro = ro.reshape(R, 3).to(F32).contiguous()
+        rd = rd.reshape(R, 3).to(F32).contiguous()
+        return _gated_field_device(fused, grid, ro, rd, z.to(F32).contiguous(), coarse, sb, total)
     if z.is_cuda and torch.cuda.is_current_stream_capturing():
         raise ValueError("occupancy gating reads the live count back to the host: it cannot be captured in a graph")
     ro = ro.reshape(R, 3).to(F32).contiguous()

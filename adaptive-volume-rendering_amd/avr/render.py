@@ -5,6 +5,7 @@ harness, utils.py:481-537, on the fused path; BASELINE configs 4 and 5).
     torchrun --nproc-per-node N -m avr.render ...   # rays of every frame sharded over N GPUs
     python -m avr.render --renderer adaptive --n-coarse 20 --philox-seed 3   # in-kernel draws: reproducible frames
     python -m avr.render --occupancy 128 [--occupancy-sigma 0.0]   # skip empty space (avr.occupancy); prints the live share
+    python -m avr.render --occupancy 128 --occupancy-count device  # the same with the live count kept on the device
 
 Renders `--frames` views on the reference's camera ring (radius, height 0.4)
 of the synthetic scene (avr.scene) or of a NewPixelNeRFNet state_dict
@@ -82,10 +83,17 @@ def main(argv=None):
                          "(default 0.0: exactly zero after the ReLU), before one cell of dilation")
     ap.add_argument("--occupancy-box", type=float, default=1.0, metavar="HALF",
                     help="the grid covers [-HALF, HALF]^3; samples outside it count as empty")
+    ap.add_argument("--occupancy-count", choices=("host", "device"), default=None,
+                    help="with --occupancy: where the live count of a gated pass is kept. host (default): read back "
+                         "once per pass to size the launches; device: never read back, worst-case buffers (40 B per "
+                         "sample), the live share is read once after the last frame")
     ap.add_argument("--out", default=None, help="directory for frame_XXX.ppm")
     args = ap.parse_args(argv)
     if args.occupancy is not None and (args.renderer != "volume" or args.t_stop is not None):
         ap.error("--occupancy needs --renderer volume and no --t-stop")
+    if args.occupancy_count is not None and args.occupancy is None:
+        ap.error("--occupancy-count needs --occupancy")
+    occupancy_count = args.occupancy_count or "host"
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -125,6 +133,7 @@ def main(argv=None):
             h = args.occupancy_box
             rend.occupancy = OccupancyGrid.from_field(net, (-h, -h, -h), (h, h, h), (args.occupancy,) * 3,
                                                       sigma_thr=args.occupancy_sigma)
+            rend.occupancy_count = occupancy_count
     K = torch.tensor([INTRINSICS], device=device)
     H = W = args.res
     x_pix = get_opencv_pixel_coordinates(H, W).reshape(1, -1, 2).to(device)
@@ -147,15 +156,21 @@ def main(argv=None):
     if dist is not None:
         dist.barrier()
     fine_samples = live_samples = 0
+    live_dev = None   # --occupancy-count device: the frames' live counts, summed on the device
     t0 = time.perf_counter()
     frames = []
     for c2w in poses:
         rend.last_fine_samples = 0
         _, rgb_f, _, _ = render(c2w)
         fine_samples += getattr(rend, "last_fine_samples", 0)
-        live_samples += getattr(rend, "last_live_samples", 0)
+        if args.occupancy is not None and occupancy_count == "device":
+            live_dev = rend.last_live_counts.clone() if live_dev is None else live_dev + rend.last_live_counts
+        else:
+            live_samples += getattr(rend, "last_live_samples", 0)
         frames.append(rgb_f)
     torch.cuda.synchronize()
+    if live_dev is not None:
+        live_samples = int(live_dev.sum().item())   # the one read, after the last frame
     if dist is not None:
         dist.barrier()
     secs = time.perf_counter() - t0
@@ -179,6 +194,7 @@ def main(argv=None):
         if args.occupancy is not None:
             # the live share: field samples evaluated over both passes' n_coarse + (n_coarse + n_fine) per ray
             line.update({"occupancy": args.occupancy, "occupancy_sigma": args.occupancy_sigma,
+                         "occupancy_count": occupancy_count,
                          "occupancy_cells_set": round(rend.occupancy.live_fraction(), 4),
                          "live_samples_fraction": round(live_samples / (args.frames * n * (2 * args.n_coarse
                                                                                           + args.n_fine)), 4)})

@@ -134,10 +134,27 @@ class VolumeRenderer(nn.Module):
         self.last_fine_samples = 0
         # Empty-space skipping (avr.occupancy; not in the reference): None = evaluate every sample; an
         # OccupancyGrid, or a list with one grid per scene, evaluates the field only where the grid is live and
-        # hands the composite exact zeros elsewhere (inference on the fused single-view path, eager only).
+        # hands the composite exact zeros elsewhere (inference on the fused single-view path).
         self.occupancy = None
         self.last_live_samples = 0          # field samples evaluated by the last gated call, both passes
         self.last_live_by_pass = (0, 0)     # (coarse, fine)
+        # Where a gated call keeps its live count: "host" (one read per pass and scene sizes the launches: eager
+        # only) or "device" (nothing is read back, every buffer is sized for the worst case, and the call may be
+        # captured in a graph: avr.graphs.GraphedRenderer). A device-mode call sets the two host counters above to
+        # None (they would need a sync) and last_live_counts to a (2,) int64 device tensor, the coarse and fine
+        # live samples summed over the scenes; captured launches write into it, so it is valid after every replay.
+        self.occupancy_count = "host"
+        self.last_live_counts = None
+
+    @property
+    def occupancy_count(self):
+        return self._occupancy_count
+
+    @occupancy_count.setter
+    def occupancy_count(self, mode):
+        if mode not in ("host", "device"):
+            raise ValueError(f"VolumeRenderer.occupancy_count must be 'host' or 'device', got {mode!r}")
+        self._occupancy_count = mode
 
     def _occupancy_grids(self, SB, radiance_field, fuse, dev):
         """The per-scene grids of a gated call, or ValueError where gating does not apply: never a quiet fallback
@@ -157,9 +174,9 @@ class VolumeRenderer(nn.Module):
         if any(g.stale(radiance_field) for g in grids):
             raise ValueError("VolumeRenderer.occupancy: a grid was built from parameters, a latent map or source "
                              "views that have changed since; rebuild it (OccupancyGrid.from_field)")
-        if dev.type == "cuda" and torch.cuda.is_current_stream_capturing():
+        if self.occupancy_count == "host" and dev.type == "cuda" and torch.cuda.is_current_stream_capturing():
             raise ValueError("VolumeRenderer.occupancy reads the live count back to the host: it cannot be captured "
-                             "in a graph")
+                             "in a graph (occupancy_count = 'device' keeps it on the device)")
         return grids
 
     @classmethod
@@ -235,9 +252,18 @@ class VolumeRenderer(nn.Module):
 
         self.last_path = "fused" if fuse else "module"
         live = []
+        on_device = grids is not None and self.occupancy_count == "device"
+        # device mode: the per-pass, per-scene live counts, written by the gated launches themselves
+        totals = torch.empty(2, SB, device=dev, dtype=torch.int64) if on_device else None
 
         def field(z, coarse):
             n = z.shape[-1]
+            if on_device:
+                from .occupancy import gated_field
+                fusedf = radiance_field.fused()
+                outs = [gated_field(fusedf, grids[b], ro[b], rd[b], z[b * R:(b + 1) * R], coarse, sb=b, count="device",
+                                    total=totals[0 if coarse else 1, b])[0] for b in range(SB)]
+                return (outs[0] if SB == 1 else torch.cat(outs, 0)).reshape(SB * R, n, 4)
             if grids is not None:   # per scene: the field on the live samples only, exact zeros elsewhere
                 from .occupancy import gated_field
                 fusedf = radiance_field.fused()
@@ -266,7 +292,10 @@ class VolumeRenderer(nn.Module):
         else:
             ff = field(z_sorted, False)
             self.last_fine_samples = z_sorted.numel()
-            if grids is not None:
+            if on_device:
+                self.last_live_by_pass = self.last_live_samples = None
+                self.last_live_counts = totals[:, 0] if SB == 1 else totals.sum(1)
+            elif grids is not None:
                 self.last_live_by_pass, self.last_live_samples = tuple(live), sum(live)
             if fast_depth:
                 # the fine weights are not returned (renderers.py:264-277): no store without autograd

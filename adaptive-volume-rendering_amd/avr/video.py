@@ -63,7 +63,8 @@ def to_uint8(img):
 
 
 def render_orbit(renderer, radiance_field, intrinsics, num_frames, radius, height, width=None, fine=True,
-                 device=None, t_stop=None, on_frame=None, occupancy=None, occupancy_sigma=0.0, occupancy_box=1.0):
+                 device=None, t_stop=None, on_frame=None, occupancy=None, occupancy_sigma=0.0, occupancy_box=1.0,
+                 occupancy_count="host"):
     """Render num_frames full frames around the orbit with `renderer`
     (e.g. avr.renderers.VolumeRenderer) and a ready radiance field. One
     renderer call per frame (all H * W rays at once), no_grad. Returns
@@ -72,7 +73,13 @@ def render_orbit(renderer, radiance_field, intrinsics, num_frames, radius, heigh
     occupancy = RES (the CLI's --occupancy / --occupancy-sigma): a RES^3 grid over
     [-occupancy_box, occupancy_box]^3 is built from the field once before the frames
     (avr.occupancy.OccupancyGrid.from_field) and gates every frame; stats then carry
-    the live share of the field samples, which is printed at the end."""
+    the live share of the field samples, which is printed at the end.
+    occupancy_count = "host" | "device" (renderer.occupancy_count for these frames): with "device" no frame reads
+    its live count back; the counts are summed on the device and read once after the last frame."""
+    if occupancy_count not in ("host", "device"):
+        raise ValueError(f"render_orbit: occupancy_count must be 'host' or 'device', got {occupancy_count!r}")
+    if occupancy is None and occupancy_count != "host":
+        raise ValueError("render_orbit: occupancy_count = 'device' needs occupancy = RES")
     width = width or height
     device = device or intrinsics.device
     K = intrinsics.reshape(1, 3, 3).to(device)
@@ -87,9 +94,12 @@ def render_orbit(renderer, radiance_field, intrinsics, num_frames, radius, heigh
     prev = getattr(renderer, "t_stop", None)
     prev_occ = getattr(renderer, "occupancy", None)
     renderer.t_stop = t_stop
+    prev_count = getattr(renderer, "occupancy_count", "host")
     if grid is not None:
         renderer.occupancy = grid
+        renderer.occupancy_count = occupancy_count
     frames, fine_samples, live_samples = [], 0, 0
+    live_dev = None   # device mode: the frames' live counts, summed on the device
     try:
         torch.cuda.synchronize(device)
         t0 = time.perf_counter()
@@ -98,7 +108,11 @@ def render_orbit(renderer, radiance_field, intrinsics, num_frames, radius, heigh
                 c2w = c2w.to(device).reshape(1, 1, 4, 4).expand(1, n, 4, 4)
                 rgb_c, rgb_f, _, _ = renderer(c2w, K, x_pix, radiance_field)
                 fine_samples += getattr(renderer, "last_fine_samples", 0)
-                live_samples += getattr(renderer, "last_live_samples", 0)
+                if grid is not None and occupancy_count == "device":
+                    live_dev = renderer.last_live_counts.clone() if live_dev is None \
+                        else live_dev + renderer.last_live_counts
+                else:
+                    live_samples += getattr(renderer, "last_live_samples", 0)
                 img = (rgb_f if fine else rgb_c)[0].reshape(height, width, 3)
                 frame = to_uint8(img.float().cpu().numpy())
                 frames.append(frame)
@@ -110,20 +124,26 @@ def render_orbit(renderer, radiance_field, intrinsics, num_frames, radius, heigh
         renderer.t_stop = prev
         if grid is not None:
             renderer.occupancy = prev_occ
+            renderer.occupancy_count = prev_count
+    if live_dev is not None:
+        live_samples = int(live_dev.sum().item())   # the one read, after the last frame
     stats = {"seconds": secs, "rays_per_s": num_frames * n / secs, "frames": num_frames,
              "rays_per_frame": n, "fine_samples": fine_samples}
     if grid is not None:
         per_ray = 2 * renderer.n_coarse + renderer.n_fine    # the coarse pass, then coarse + fine positions again
         stats["live_share"] = live_samples / max(num_frames * n * per_ray, 1)
+        stats["occupancy_count"] = occupancy_count
         print(f"occupancy {occupancy}^3: {stats['live_share']:.4f} of the field samples were live")
     return frames, stats
 
 
-def generate_video(model_input, num_frames, radius, net, model, fine=True):
+def generate_video(model_input, num_frames, radius, net, model, fine=True, occupancy=None, occupancy_count="host"):
     """utils.py:481-537 with the same arguments: encode the first source view
     of model_input into `net`, then render the orbit through `model`
     (a RadFieldAndRenderer). A net whose latent was set with encode_latent()
-    keeps it (no `images` needed); otherwise the source view is encoded."""
+    keeps it (no `images` needed); otherwise the source view is encoded.
+    occupancy = RES, occupancy_count = "host" | "device": render_orbit's empty-space skipping (not in the
+    reference; off by default)."""
     intrinsics = model_input["intrinsics"][0:1, 0, ...]
     if "images" in model_input and net.encoder.latent.shape[-1] <= 1:   # no latent yet
         gt = model_input["images"]
@@ -132,7 +152,8 @@ def generate_video(model_input, num_frames, radius, net, model, fine=True):
         src = gt[0:1, 0:1, ...].reshape(1, -1, sl, sl, 3).permute(0, 1, 4, 2, 3)
         net.encode(src, model_input["cam2world"][0:1, 0:1, ...], model_input["focal"][0, 0], model_input["c"][0, 0, :])
     sl = int(model_input.get("resolution", 0)) or int(np.sqrt(model_input["images"].shape[2]))
-    frames, stats = render_orbit(model.renderer, net, intrinsics, num_frames, radius, sl, fine=fine)
+    frames, stats = render_orbit(model.renderer, net, intrinsics, num_frames, radius, sl, fine=fine,
+                                 occupancy=occupancy, occupancy_count=occupancy_count)
     print(f"it takes {stats['seconds']} seconds to render a video")
     return frames
 

@@ -104,15 +104,23 @@ __device__ __forceinline__ void store_relu(floatx4* slab, const floatx4 (&acc)[N
   }
 }
 
-template <int NT>
+// CNT (avr_field_fwd_points_counted): launched over a.M = capacity rows, the row count M read from a.count on the
+// device by a wave-uniform load; a workgroup whose first row is at or beyond it leaves before anything else, the
+// last live one clamps and guards its tail rows against it as the uncounted kernel does against a.M.
+template <int NT, bool CNT = false>
 __global__ void __launch_bounds__(256, 1) field_fwd_kernel(FieldArgs a) {
+  int64_t M = a.M;
+  if constexpr (CNT) {
+    M = counted_rows(a);
+    if ((int64_t)blockIdx.x * (kFieldWaves * kSPW) >= M) return;
+  }
   extern __shared__ floatx4 lds[];
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
   const int j = lane & 15, g = lane >> 4;
   floatx4* slab = lds + (size_t)wid * (NT > kInTiles ? NT : kInTiles) * 64;
   const int64_t m = ((int64_t)blockIdx.x * kFieldWaves + wid) * kSPW + j;
-  const bool valid = m < a.M;
-  const int64_t mm = valid ? m : a.M - 1;
+  const bool valid = m < M;
+  const int64_t mm = valid ? m : M - 1;
 
   // ---- sample geometry, z_feature (features 16t + 4g + r of this lane's sample -> slab[t][lane])
   const SampleGeom sg = sample_geom(a, mm);
@@ -258,12 +266,13 @@ static int fp32_width(int d_hidden, F f) {
   return fail(AVR_E_UNSUPPORTED, "field: d_hidden %d", d_hidden);
 }
 
-template <int NT>
+template <int NT, bool CNT = false>
 static int launch_field(const FieldArgs& a, hipStream_t s) {
   const size_t shm = (size_t)kFieldWaves * (NT > kInTiles ? NT : kInTiles) * 64 * sizeof(floatx4);
   const int64_t per_block = kFieldWaves * kSPW;
-  return launch_lds<field_fwd_kernel<NT>>("field_fwd_kernel", "field: too many points",
-                                          (a.M + per_block - 1) / per_block, 1, 1, 64 * kFieldWaves, shm, shm, s, a);
+  return launch_lds<field_fwd_kernel<NT, CNT>>("field_fwd_kernel", "field: too many points",
+                                               (a.M + per_block - 1) / per_block, 1, 1, 64 * kFieldWaves, shm, shm, s,
+                                               a);
 }
 
 // (the dynamic-LDS limit is set per call on purpose: it depends on d_latent, which can grow between calls)
@@ -324,6 +333,20 @@ static int dispatch_field(const avr_field_dims* dims, const FieldArgs& a, hipStr
   AVR_REQUIRE(!dims->spade && !(dims->beta > 0.f), "field: use_spade / Softplus nets run on the x3 path only");
   AVR_REQUIRE(dims->precision == AVR_FIELD_FP32, "field: unknown precision %d", dims->precision);
   return fp32_width(d_hidden, [&](auto nt) { return launch_field<decltype(nt)::value>(a, s); });
+}
+
+// The counted launch (avr_field_fwd_points_counted; a.count set): ReLU nets without BatchNorm / use_spade, either
+// precision.
+static int dispatch_field_counted(const avr_field_dims* dims, const FieldArgs& a, hipStream_t s) {
+  if (dims->bn || dims->spade || dims->beta > 0.f)
+    return fail(AVR_E_UNSUPPORTED, "avr_field_fwd_points_counted: BatchNorm, use_spade and Softplus nets have no "
+                                   "counted kernel");
+  if (dims->precision == AVR_FIELD_X3) return dispatch_field_x3_counted(dims->d_hidden, a, s);
+  AVR_REQUIRE(packed_precision(a.packed) != AVR_FIELD_X3,
+              "field: the blob was packed for AVR_FIELD_X3 (no fp32 lin_in / fc_0 / fc_1 fragments): pack it with "
+              "AVR_FIELD_FP32 to run the fp32 kernel");
+  AVR_REQUIRE(dims->precision == AVR_FIELD_FP32, "field: unknown precision %d", dims->precision);
+  return fp32_width(dims->d_hidden, [&](auto nt) { return launch_field<decltype(nt)::value, true>(a, s); });
 }
 
 }  // namespace avr
@@ -545,4 +568,23 @@ extern "C" int avr_field_fwd_points(const avr_field_dims* dims, const avr_view_d
   a.out = reinterpret_cast<float4*>(out);
   if (a.M == 0) return AVR_OK;
   return dispatch_field(dims, a, as_stream(stream));
+}
+
+// avr_field_fwd_points over `capacity` rows with the row count read from device memory (include/avr.h).
+extern "C" int avr_field_fwd_points_counted(const avr_field_dims* dims, const avr_view_desc* view, const float* packed,
+                                            const float* table, const float* xyz, const float* viewdirs,
+                                            int64_t capacity, const int64_t* n_points, float* out, void* stream) {
+  FieldArgs a{};
+  int rc = field_common(dims, view, packed, table, &a);
+  if (rc) return rc;
+  AVR_REQUIRE(capacity >= 0, "avr_field_fwd_points_counted: negative capacity");
+  AVR_REQUIRE(capacity == 0 || (xyz && viewdirs && out && n_points), "avr_field_fwd_points_counted: null pointer");
+  AVR_REQUIRE((((uintptr_t)out) & 15) == 0 && (((uintptr_t)n_points) & 7) == 0,
+              "avr_field_fwd_points_counted: out rows must be 16-B aligned, n_points 8-B aligned");
+  a.xyz = xyz; a.vd = viewdirs; a.n_samples = 1;
+  a.M = capacity;
+  a.count = n_points;
+  a.out = reinterpret_cast<float4*>(out);
+  if (a.M == 0) return AVR_OK;
+  return dispatch_field_counted(dims, a, as_stream(stream));
 }

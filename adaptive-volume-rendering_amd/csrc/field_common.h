@@ -136,7 +136,15 @@ struct FieldArgs {
   View views[AVR_MAX_SCENES];
   unsigned long long* stamps;  // diagnostic builds (-DAVR_STAMPS) only: per-block phase clocks (waves 0, 4)
   int debug;                   // diagnostic builds only: experiment flags (1: every fc layer uses block 0's weights)
+  const int64_t* count;        // counted launches (avr_field_fwd_points_counted): the row count on the device, M = capacity
 };
+
+// The row count of a counted launch: *a.count (one scalar load, wave-uniform), held to 0 .. a.M (the capacity the
+// buffers were sized for).
+__device__ __forceinline__ int64_t counted_rows(const FieldArgs& a) {
+  const int64_t n = *a.count;
+  return n < a.M ? n : a.M;
+}
 
 #ifdef AVR_STAMPS
 #define AVR_STAMP(k)                                                                          \
@@ -343,6 +351,8 @@ inline bool env_eight_waves(const char* name) {
 }
 
 int dispatch_field_x3(int d_hidden, const FieldArgs& a, hipStream_t s);
+// The same over a.M = capacity rows with the row count read from *a.count on the device (ReLU inference nets)
+int dispatch_field_x3_counted(int d_hidden, const FieldArgs& a, hipStream_t s);
 // The packed blobs' layouts for dims (field_pack.hip; both check dims), for the entry points and the kernels of
 // other units (bn_train.hip: the layer-by-layer BatchNorm training GEMMs read the same fragments).
 int field_layout(const avr_field_dims* d, Layout* L);

@@ -227,8 +227,21 @@ __device__ __forceinline__ void save_layer(const FieldArgs& a, int layer, const 
 // table follows as for every net (its bias is in the table, not folded into the previous layer).
 // ACT: the MLP's activation (x3_gemm.h act1: 0 ReLU, 1 Softplus(a.beta)); the split scale of a layer input
 // comes from act_bound of the max of max(0, pre-activation), its epilogue's usual reduction.
-template <int FT, int NW, bool SAVE, bool BN = false, bool SPADE = false, int ACT = 0>
+// CNT (avr_field_fwd_points_counted; single scene, ReLU inference): launched over a.M = capacity rows, the row
+// count M read from a.count on the device by a wave-uniform load. A workgroup whose first row is at or beyond it
+// leaves before its first barrier, LDS write or s_setprio; the last live one clamps and guards its tail rows
+// against M as the uncounted kernel does against a.M.
+template <int FT, int NW, bool SAVE, bool BN = false, bool SPADE = false, int ACT = 0, bool CNT = false>
 __global__ void __launch_bounds__(64 * NW, 1) field_x3_kernel(FieldArgs a) {
+  static_assert(!CNT || (!SAVE && !BN && !SPADE && ACT == 0), "counted: ReLU inference only");
+  int64_t counted = 0;
+  if constexpr (CNT) {
+    counted = counted_rows(a);
+    if ((int64_t)blockIdx.x * kX3Samples >= counted) return;
+  }
+  // the scene's rows: a.M, read where it is used (the code of the kernels without CNT is what it was before CNT
+  // existed, instruction for instruction), or the device count
+#define X3_ROWS (CNT ? counted : a.M)
   constexpr int HID = 16 * FT * NW;
   using P = LdsPlan<HID>;
   constexpr int KC = P::KC;
@@ -269,7 +282,7 @@ __global__ void __launch_bounds__(64 * NW, 1) field_x3_kernel(FieldArgs a) {
     lblk = blockIdx.x - (int64_t)scene * a.blocks_per_scene;
   }
   const int64_t base = lblk * kX3Samples;
-  const int64_t roff = (int64_t)scene * a.M;
+  const int64_t roff = (int64_t)scene * X3_ROWS;
   const Layout& L = a.L;
   const uint4* P16 = reinterpret_cast<const uint4*>(a.packed);  // 16-B units
 
@@ -295,7 +308,7 @@ __global__ void __launch_bounds__(64 * NW, 1) field_x3_kernel(FieldArgs a) {
     {
       const int s = 16 * (wid & 3) + j;
       const int64_t m = base + s;
-      const int64_t mm = m < a.M ? m : a.M - 1;
+      const int64_t mm = m < X3_ROWS ? m : X3_ROWS - 1;
       const SampleGeom geo = SAVE ? sample_geom_pts(a.views[scene], a.xyz + 3 * roff, a.vd + 3 * roff, mm)
                                   : sample_geom_scene(a, multi ? a.views[scene] : a.v, roff, mm);
       if (g == 0 && wid < 4) {
@@ -348,7 +361,7 @@ __global__ void __launch_bounds__(64 * NW, 1) field_x3_kernel(FieldArgs a) {
       // the training forward also keeps z_feature (lin_in's input, the operand of its weight gradient): the
       // values this lane owns, the padding columns up to zf_ld as zeros
       const int64_t m = base + 16 * (wid & 3) + j;
-      if (m < a.M) {
+      if (m < X3_ROWS) {
         float* zr = a.zf + (roff + m) * a.zf_ld;
 #pragma unroll
         for (int i = 0; i < PES; ++i)
@@ -411,7 +424,7 @@ __global__ void __launch_bounds__(64 * NW, 1) field_x3_kernel(FieldArgs a) {
 #pragma unroll
       for (int sg = 0; sg < 4; ++sg) {
         const int64_t m = base + 16 * sg + j;
-        const int64_t mm = m < a.M ? m : a.M - 1;
+        const int64_t mm = m < X3_ROWS ? m : X3_ROWS - 1;
         h[ft][sg] = *reinterpret_cast<const floatx4*>(a.h_in + (roff + mm) * HID + 16 * (FT * wid + ft) + 4 * g);
       }
   }
@@ -558,7 +571,7 @@ __global__ void __launch_bounds__(64 * NW, 1) field_x3_kernel(FieldArgs a) {
 #pragma unroll
       for (int sg = 0; sg < 4; ++sg) {
         const int64_t m = base + 16 * sg + j;
-        if (m < a.M)
+        if (m < X3_ROWS)
           __builtin_nontemporal_store(h[ft][sg] * f, reinterpret_cast<floatx4*>(a.h_out + (roff + m) * HID +
                                                                                 16 * (FT * wid + ft) + 4 * g));
       }
@@ -586,7 +599,7 @@ __global__ void __launch_bounds__(64 * NW, 1) field_x3_kernel(FieldArgs a) {
     int snval = 0;
     if constexpr (SAVE) {
       sact = a.act + (int64_t)lout * a.act_stride + (roff + base) * HID;
-      snval = a.M - base < 64 ? (int)(a.M - base) : 64;
+      snval = X3_ROWS - base < 64 ? (int)(X3_ROWS - base) : 64;
     }
 #pragma unroll
     for (int sg = 0; sg < 4; ++sg) {
@@ -647,7 +660,7 @@ __global__ void __launch_bounds__(64 * NW, 1) field_x3_kernel(FieldArgs a) {
     }
     const int s = 16 * wid + j;
     const int64_t m = base + s;
-    if (g == 0 && m < a.M) {
+    if (g == 0 && m < X3_ROWS) {
       float4 o = *reinterpret_cast<const float4*>(a.packed + L.b_out);
 #pragma unroll
       for (int v = 0; v < NW; ++v) {
@@ -693,7 +706,7 @@ __global__ void __launch_bounds__(64 * NW, 1) field_x3_kernel(FieldArgs a) {
   o *= 1.0f / S;
   AVR_STAMP(26);
   const int64_t m = base + 16 * wid + j;
-  if (g == 0 && m < a.M)
+  if (g == 0 && m < X3_ROWS)
     a.out[roff + m] = make_float4(sigmoidf_(o.x), sigmoidf_(o.y), sigmoidf_(o.z), fmaxf(o.w, 0.f));
   if constexpr (SAVE) {
     // the layer maxima: one atomic per workgroup and layer, issued last (nothing waits on them here;
@@ -702,6 +715,7 @@ __global__ void __launch_bounds__(64 * NW, 1) field_x3_kernel(FieldArgs a) {
     if (a.act_max && wid == 0 && lane < nl) publish_max(a.act_max + lane, tail->lmax[lane]);
     if (a.zf_max && threadIdx.x == 64) publish_max(a.zf_max, tail->zmax);
   }
+#undef X3_ROWS
 }
 
 // ---- lin_z / scale_z tables on the same split-fp16 GEMM (x3 fields; the fp32 field keeps
@@ -816,13 +830,13 @@ int dispatch_table_x3(const float* packed, const Layout& L, const float* latent,
   });
 }
 
-template <int FT, int NW, bool SAVE, bool BN = false, bool SPADE = false, int ACT = 0>
+template <int FT, int NW, bool SAVE, bool BN = false, bool SPADE = false, int ACT = 0, bool CNT = false>
 static int launch_x3(const FieldArgs& a, hipStream_t s) {
   const size_t shm = LdsPlan<16 * FT * NW>::BYTES;
   const int64_t blocks = (SAVE || a.n_scenes > 1) ? a.blocks_per_scene * a.n_scenes
                                                   : (a.M + kX3Samples - 1) / kX3Samples;
-  return launch_lds<field_x3_kernel<FT, NW, SAVE, BN, SPADE, ACT>>("field_x3_kernel", "field: too many points",
-                                                                   blocks, 1, 1, 64 * NW, shm, shm, s, a);
+  return launch_lds<field_x3_kernel<FT, NW, SAVE, BN, SPADE, ACT, CNT>>("field_x3_kernel", "field: too many points",
+                                                                        blocks, 1, 1, 64 * NW, shm, shm, s, a);
 }
 
 // d_hidden 512 runs 8 waves x 4 tiles where the variant has that layout (inference: +2.7-4.7 % over the 4-wave
@@ -856,6 +870,15 @@ int dispatch_field_x3(int d_hidden, const FieldArgs& a, hipStream_t s) {
     });
   return x3_width<0>(d_hidden, env_eight_waves("AVR_X3_WAVES"), what, [&](auto ft, auto nw) {
     return launch_x3<decltype(ft)::value, decltype(nw)::value, false>(a, s);
+  });
+}
+
+// The counted launch (a.count set, a.M = capacity): the ReLU inference kernels of dispatch_field_x3's last case.
+int dispatch_field_x3_counted(int d_hidden, const FieldArgs& a, hipStream_t s) {
+  AVR_REQUIRE(a.count && !a.L.bn && !a.L.spade && !(a.beta > 0.f) && !a.act && a.n_scenes <= 1 && !a.h_in && !a.h_out,
+              "field x3 counted: single-scene ReLU inference only");
+  return x3_width<0>(d_hidden, env_eight_waves("AVR_X3_WAVES"), "field x3 counted", [&](auto ft, auto nw) {
+    return launch_x3<decltype(ft)::value, decltype(nw)::value, false, false, false, 0, true>(a, s);
   });
 }
 

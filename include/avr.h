@@ -724,6 +724,45 @@ int avr_occ_compact(const float* ro, const float* rd, const float* z, const uint
 int avr_occ_expand(const float* field_c, const uint64_t* mask, const int64_t* offsets, int64_t n_rays, int n_samples,
                    int64_t n_live, float* field, void* stream);
 
+/* ------------------------------------------- occupancy grid, device-side count
+ * Additions within ABI 18 (no version change; DESIGN.md "Occupancy grid: device-side live count"): the same gated
+ * chain with the live count kept on the device from avr_occ_classify to avr_occ_expand, so that no host read sizes a
+ * launch and the chain can be recorded in a HIP-graph capture:
+ *   classify -> avr_occ_scan -> avr_occ_compact_counted -> avr_field_fwd_points_counted -> avr_occ_expand_counted
+ * The compacted buffers (xyz, viewdirs (capacity, 3); field_c (capacity, 4)) are sized by a host `capacity`, 0 <=
+ * *n_live <= capacity <= n_rays * n_samples; a device count outside 0 .. capacity is held to that range by every
+ * kernel that reads it, so no row at or beyond capacity is touched.
+ *   avr_occ_scan: counts (n_rays) int32 -> offsets (n_rays) int64 = the exclusive prefix sums, *total (device int64)
+ *     = the sum. total is always written (0 for n_rays == 0: one tiny launch), no memset by the caller. Every n_rays
+ *     avr_occ_classify accepts. Reduce, then scan: at most three launches (one up to AVR_OCC_SCAN_RAYS rays), each
+ *     workgroup owning AVR_OCC_SCAN_RAYS consecutive rays; no kernel waits on another workgroup; integer adds only,
+ *     so the result is exact and reproducible for every sum that fits int64. Between its launches offsets holds the
+ *     workgroup sums (no scratch buffer). offsets and total 8-B aligned.
+ *   avr_occ_compact_counted / avr_occ_expand_counted: avr_occ_compact / avr_occ_expand with n_live read from the
+ *     device (8-B aligned). Compact writes rows [0, *n_live) of xyz and viewdirs and nothing beyond; expand writes
+ *     every element of field and never reads a field_c row at or beyond *n_live (with *n_live == 0 it reads neither
+ *     mask nor offsets). capacity == 0 launches nothing (expand then leaves field unwritten: there is no compacted
+ *     buffer to expand; avr_occ_expand with n_live = 0 zero-fills).
+ *   avr_field_fwd_points_counted: avr_field_fwd_points launched over `capacity` rows, with every use of the row
+ *     count taken from *n_points (device int64, 8-B aligned). Rows [*n_points, capacity) of out, xyz and viewdirs are
+ *     neither read nor written; rows below the count are bit-equal to avr_field_fwd_points with n_points = the count
+ *     (same workgroup membership). A workgroup whose first row is at or beyond the count returns at once. Both
+ *     precisions, ReLU nets without BatchNorm or use_spade at every d_hidden of the fused path; a BatchNorm,
+ *     use_spade or Softplus net is AVR_E_UNSUPPORTED (no counted kernel, never another path).
+ * Checked before any launch (AVR_E_INVALID): null pointers, negative n_rays / capacity, n_samples out of range,
+ * capacity above n_rays * n_samples, misaligned field rows or counts. capacity == 0 or n_rays == 0 returns AVR_OK
+ * with no launch, except that avr_occ_scan writes *total.                                                          */
+#define AVR_OCC_SCAN_RAYS 2048
+int avr_occ_scan(const int32_t* counts, int64_t n_rays, int64_t* offsets, int64_t* total, void* stream);
+int avr_occ_compact_counted(const float* ro, const float* rd, const float* z, const uint64_t* mask,
+                            const int64_t* offsets, int64_t n_rays, int n_samples, const int64_t* n_live,
+                            int64_t capacity, float* xyz, float* viewdirs, void* stream);
+int avr_occ_expand_counted(const float* field_c, const uint64_t* mask, const int64_t* offsets, int64_t n_rays,
+                           int n_samples, const int64_t* n_live, int64_t capacity, float* field, void* stream);
+int avr_field_fwd_points_counted(const avr_field_dims* dims, const avr_view_desc* view, const float* packed,
+                                 const float* table, const float* xyz, const float* viewdirs, int64_t capacity,
+                                 const int64_t* n_points, float* out, void* stream);
+
 /* ------------------------------------------------------------ measurement
  * Streaming device copy dst[0, n_bytes) = src[0, n_bytes) (16-B aligned,
  * n_bytes a multiple of 16): the achievable-HBM yardstick bench.py reports
