@@ -222,6 +222,12 @@ _SIGS = {
     "avr_occ_expand_counted": [c_void_p, c_void_p, c_void_p, i64, c_int, c_void_p, i64, c_void_p, c_void_p],
     "avr_field_fwd_points_counted": [ctypes.POINTER(FieldDims), ctypes.POINTER(ViewDesc), c_void_p, c_void_p,
                                      c_void_p, c_void_p, i64, c_void_p, c_void_p, c_void_p],
+    "avr_march_classify": [ctypes.POINTER(OccGrid), c_void_p, c_void_p, c_void_p, c_void_p, i64, c_int, c_int, c_int,
+                           c_float, c_void_p, c_void_p, c_void_p],
+    "avr_march_compact_counted": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, i64, c_int, c_int, c_int, c_void_p,
+                                  i64, c_void_p, c_void_p, c_void_p],
+    "avr_march_composite_masked": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, i64, i64, c_int, c_int, c_int,
+                                   c_float, c_float, c_void_p, c_void_p, c_int, c_void_p],
     "avr_stream_copy": [c_void_p, c_void_p, i64, c_void_p],
     "avr_stream_fill": [c_void_p, i64, c_uint32, c_void_p],
 }

@@ -31,6 +31,12 @@ captured classify launches read the grids' bits through their addresses, which t
 live counts. The graph's pool keeps the worst-case compacted buffers (40 B per sample) for as long as the graph
 lives. A re-capture caused by a weight change meets the renderer's stale-grid ValueError, as an eager call would:
 rebuild the grid (OccupancyGrid.from_field), assign it to renderer.occupancy, then call refresh().
+
+Early termination: a renderer with `t_stop` set is accepted when `renderer.t_stop_count == "device"` (the fine pass's
+classify -> scan -> compact -> field -> composite chain per 64-sample chunk keeps every count on the device; the
+host-read mode is refused). With a grid set too, the coarse pass follows `occupancy_count`, which must then be
+"device" as above. `renderer.last_fine_counts` holds the replay's evaluated fine samples; the graph's pool keeps the
+chain's worst-case buffers (40 B per ray and chunk sample).
 """
 import torch
 
@@ -55,8 +61,9 @@ class GraphedRenderer:
     """
 
     def __init__(self, renderer, net, cam2world, intrinsics, x_pix, warmup=2):
-        if renderer.t_stop is not None:
-            raise ValueError("GraphedRenderer: early termination sizes its launches on the host (t_stop must be None)")
+        if renderer.t_stop is not None and getattr(renderer, "t_stop_count", "host") != "device":
+            raise ValueError("GraphedRenderer: early termination sizes its launches on the host (t_stop must be None, "
+                             "or renderer.t_stop_count 'device')")
         if getattr(renderer, "occupancy", None) is not None and \
                 getattr(renderer, "occupancy_count", "host") != "device":
             raise ValueError("GraphedRenderer: occupancy gating reads the live count back to the host "

@@ -285,6 +285,67 @@ def march_fine(ro, rd, z, field_fn, t_stop, white_back=True, infinity=1.8, chunk
     return rgb, dist, evaluated
 
 
+def march_fine_device(ro, rd, z, field_points_fn, t_stop, white_back=True, infinity=1.8, chunk=64, grid=None,
+                      total=None):
+    """march_fine with every count kept on the device (include/avr.h "fine pass, early termination on the
+    device"), optionally gated by an avr.occupancy.OccupancyGrid: a sample reaches the field iff its ray is still
+    alive and its cell is occupied (grid=None: every cell). Per chunk: avr_march_classify -> avr_occ_scan ->
+    avr_march_compact_counted -> field_points_fn -> avr_march_composite_masked; no host read, no atomics and no
+    torch kernel (torch.empty only), so the call is legal on a capturing stream and bit-reproducible.
+    field_points_fn(xyz, viewdirs, n_live_dev) -> (capacity, 4) evaluates the field on the first *n_live_dev rows
+    of xyz, viewdirs (capacity, 3) (FusedField.forward_points_scene_counted); rows at or beyond the count are
+    never read. The buffers are sized for the worst case, R * chunk rows, once, and reused by every chunk.
+    Returns rgb (R, 3), dist (R,) and the number of field samples evaluated, a 0-dim int64 device tensor (`total`
+    when given: overwritten, not added to)."""
+    R, N = z.shape
+    chunk = int(chunk)
+    if not 1 <= chunk <= 64:
+        raise ValueError(f"march_fine_device: chunk {chunk} outside 1..64")
+    ro, rd, z = _f32c(ro.reshape(R, 3)), _f32c(rd.reshape(R, 3)), _f32c(z)
+    require_device(ro, rd, z)
+    dev, s = z.device, stream_of(z)
+    if total is None:
+        total = torch.empty((), device=dev, dtype=torch.int64)
+    elif total.dtype != torch.int64 or total.numel() != 1 or total.device != dev:
+        raise ValueError("march_fine_device: total must be one int64 on z's device")
+    gdesc = None
+    if grid is not None:
+        require_device(grid.bits)
+        gdesc = ctypes.byref(grid.desc)
+    rgb = torch.empty(R, 3, device=dev, dtype=F32)
+    dist = torch.empty(R, device=dev, dtype=F32)
+    n_live = torch.empty((), device=dev, dtype=torch.int64)
+    if N == 0:
+        raise ValueError("march_fine_device: z has no samples")
+    if R == 0:
+        call("avr_occ_scan", None, 0, None, ptr(total), s)   # *total = 0
+        return rgb, dist, total
+    C0 = min(chunk, N)
+    cap = R * C0
+    state = torch.empty(_lib.size_query("avr_march_state_bytes", R), device=dev, dtype=torch.uint8)
+    unused = torch.empty(R, device=dev, dtype=torch.int32)   # avr_march_init's active list
+    mask = torch.empty(R, device=dev, dtype=torch.int64)
+    counts = torch.empty(R, device=dev, dtype=torch.int32)
+    offsets = torch.empty(R, device=dev, dtype=torch.int64)
+    xyz = torch.empty(cap, 3, device=dev, dtype=F32)
+    vd = torch.empty(cap, 3, device=dev, dtype=F32)
+    call("avr_march_init", R, ptr(state), ptr(unused), s)
+    for c0 in range(0, N, chunk):
+        C = min(chunk, N - c0)
+        call("avr_march_classify", gdesc, ptr(ro), ptr(rd), ptr(z), ptr(state), R, N, c0, C, float(t_stop), ptr(mask),
+             ptr(counts), s)
+        call("avr_occ_scan", ptr(counts), R, ptr(offsets), ptr(n_live), s)
+        call("avr_march_compact_counted", ptr(ro), ptr(rd), ptr(z), ptr(mask), ptr(offsets), R, N, c0, C, ptr(n_live),
+             R * C, ptr(xyz), ptr(vd), s)
+        f_c = field_points_fn(xyz, vd, n_live)
+        if f_c.dtype != F32 or not f_c.is_contiguous() or f_c.numel() != cap * 4:
+            raise ValueError("march_fine_device: field_points_fn must return a contiguous fp32 (capacity, 4) tensor")
+        call("avr_march_composite_masked", ptr(z), ptr(f_c), ptr(mask), ptr(offsets), ptr(n_live), R * C, R, N, c0, C,
+             float(infinity), float(t_stop), ptr(state), ptr(total), 1 if c0 else 0, s)
+    call("avr_march_finish", ptr(state), R, 1 if white_back else 0, ptr(rgb), ptr(dist), s)
+    return rgb, dist, total
+
+
 def sample_coarse_rays(near, far, n_samples, noise=None, seed=0, offset=0):
     """sample_coarse with per-ray bounds near/far (R,) -> z (R, n_samples)
     (renderers.py:4-24 called with tensors, as AdaptiveVolumeRenderer does)."""

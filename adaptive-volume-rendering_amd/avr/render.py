@@ -6,6 +6,7 @@ harness, utils.py:481-537, on the fused path; BASELINE configs 4 and 5).
     python -m avr.render --renderer adaptive --n-coarse 20 --philox-seed 3   # in-kernel draws: reproducible frames
     python -m avr.render --occupancy 128 [--occupancy-sigma 0.0]   # skip empty space (avr.occupancy); prints the live share
     python -m avr.render --occupancy 128 --occupancy-count device  # the same with the live count kept on the device
+    python -m avr.render --t-stop 1e-3 --t-stop-count device [--occupancy 128]   # termination without host reads
 
 Renders `--frames` views on the reference's camera ring (radius, height 0.4)
 of the synthetic scene (avr.scene) or of a NewPixelNeRFNet state_dict
@@ -87,10 +88,21 @@ def main(argv=None):
                     help="with --occupancy: where the live count of a gated pass is kept. host (default): read back "
                          "once per pass to size the launches; device: never read back, worst-case buffers (40 B per "
                          "sample), the live share is read once after the last frame")
+    ap.add_argument("--t-stop-count", choices=("host", "device"), default=None,
+                    help="with --t-stop: where early termination keeps its counts. host (default): the active-ray "
+                         "count is read back after every 64-sample chunk; device: never read back, worst-case buffers "
+                         "(40 B per ray and chunk sample), combinable with --occupancy, the evaluated fine samples are "
+                         "read once after the last frame")
     ap.add_argument("--out", default=None, help="directory for frame_XXX.ppm")
     args = ap.parse_args(argv)
-    if args.occupancy is not None and (args.renderer != "volume" or args.t_stop is not None):
-        ap.error("--occupancy needs --renderer volume and no --t-stop")
+    if args.t_stop_count is not None and args.t_stop is None:
+        ap.error("--t-stop-count needs --t-stop")
+    t_stop_count = args.t_stop_count or "host"
+    if t_stop_count == "device" and args.renderer != "volume":
+        ap.error("--t-stop-count device needs --renderer volume")
+    if args.occupancy is not None and (args.renderer != "volume"
+                                       or (args.t_stop is not None and t_stop_count != "device")):
+        ap.error("--occupancy needs --renderer volume and no --t-stop (or --t-stop-count device)")
     if args.occupancy_count is not None and args.occupancy is None:
         ap.error("--occupancy-count needs --occupancy")
     occupancy_count = args.occupancy_count or "host"
@@ -127,6 +139,7 @@ def main(argv=None):
         rend = VolumeRenderer(args.near, args.far, args.n_coarse, args.n_fine, 0, 0.01, True)
         rend.seed = 1234
         rend.t_stop = args.t_stop
+        rend.t_stop_count = t_stop_count
         samples_per_ray = args.n_coarse + args.n_fine
         if args.occupancy is not None:   # once per scene, before the frames (after the broadcast: every rank's own)
             from .occupancy import OccupancyGrid
@@ -157,12 +170,16 @@ def main(argv=None):
         dist.barrier()
     fine_samples = live_samples = 0
     live_dev = None   # --occupancy-count device: the frames' live counts, summed on the device
+    fine_dev = None   # --t-stop-count device: the frames' evaluated fine samples, likewise
     t0 = time.perf_counter()
     frames = []
     for c2w in poses:
         rend.last_fine_samples = 0
         _, rgb_f, _, _ = render(c2w)
-        fine_samples += getattr(rend, "last_fine_samples", 0)
+        if t_stop_count == "device":
+            fine_dev = rend.last_fine_counts.clone() if fine_dev is None else fine_dev + rend.last_fine_counts
+        else:
+            fine_samples += getattr(rend, "last_fine_samples", 0)
         if args.occupancy is not None and occupancy_count == "device":
             live_dev = rend.last_live_counts.clone() if live_dev is None else live_dev + rend.last_live_counts
         else:
@@ -171,6 +188,8 @@ def main(argv=None):
     torch.cuda.synchronize()
     if live_dev is not None:
         live_samples = int(live_dev.sum().item())   # the one read, after the last frame
+    if fine_dev is not None:
+        fine_samples = int(fine_dev.item())
     if dist is not None:
         dist.barrier()
     secs = time.perf_counter() - t0
@@ -188,7 +207,8 @@ def main(argv=None):
         line = {"renderer": args.renderer, "samples_per_ray": samples_per_ray,
                 "frames": args.frames, "res": args.res, "rays_per_frame": n, "n_gpus": world,
                 "seconds": round(secs, 4), "rays_per_s": round(args.frames * n / secs, 1),
-                "t_stop": args.t_stop, "precision": args.precision, "sigma_bias": args.sigma_bias,
+                "t_stop": args.t_stop, "t_stop_count": t_stop_count, "precision": args.precision,
+                "sigma_bias": args.sigma_bias,
                 "fine_samples_evaluated": fine_samples,
                 "fine_samples_fraction": round(fine_samples / total_fine, 4)}
         if args.occupancy is not None:

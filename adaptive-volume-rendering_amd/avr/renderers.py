@@ -145,6 +145,13 @@ class VolumeRenderer(nn.Module):
         # live samples summed over the scenes; captured launches write into it, so it is valid after every replay.
         self.occupancy_count = "host"
         self.last_live_counts = None
+        # Where early termination keeps its counts: "host" (ops.march_fine: the active-ray count is read back after
+        # every chunk: eager only, refuses a grid) or "device" (ops.march_fine_device: nothing is read back, the fine
+        # pass is terminated and, with `occupancy` set, gated by one chain that can be captured in a graph). A
+        # device-mode call sets last_fine_samples to None and last_fine_counts to a 0-dim int64 device tensor, the
+        # fine samples that reached the field summed over chunks and scenes; captured launches write it.
+        self.t_stop_count = "host"
+        self.last_fine_counts = None
 
     @property
     def occupancy_count(self):
@@ -156,6 +163,16 @@ class VolumeRenderer(nn.Module):
             raise ValueError(f"VolumeRenderer.occupancy_count must be 'host' or 'device', got {mode!r}")
         self._occupancy_count = mode
 
+    @property
+    def t_stop_count(self):
+        return self._t_stop_count
+
+    @t_stop_count.setter
+    def t_stop_count(self, mode):
+        if mode not in ("host", "device"):
+            raise ValueError(f"VolumeRenderer.t_stop_count must be 'host' or 'device', got {mode!r}")
+        self._t_stop_count = mode
+
     def _occupancy_grids(self, SB, radiance_field, fuse, dev):
         """The per-scene grids of a gated call, or ValueError where gating does not apply: never a quiet fallback
         to the ungated render."""
@@ -163,8 +180,9 @@ class VolumeRenderer(nn.Module):
         grids = list(occ) if isinstance(occ, (list, tuple)) else [occ]
         if torch.is_grad_enabled():
             raise ValueError("VolumeRenderer.occupancy is inference only: call under torch.no_grad()")
-        if self.t_stop is not None:
-            raise ValueError("VolumeRenderer.occupancy cannot be combined with t_stop")
+        if self.t_stop is not None and self.t_stop_count != "device":
+            raise ValueError("VolumeRenderer.occupancy cannot be combined with t_stop (t_stop_count = 'device' "
+                             "terminates and gates the fine pass in one chain)")
         if len(grids) != SB:
             raise ValueError(f"VolumeRenderer.occupancy holds {len(grids)} grid(s) for {SB} scene(s)")
         if self.n_coarse + self.n_fine > _lib.OCC_MAX_SAMPLES:
@@ -207,6 +225,34 @@ class VolumeRenderer(nn.Module):
             self.last_fine_samples += n
         return torch.cat(rgbs, 0), torch.cat(dists, 0)
 
+    def _check_termination_device(self, radiance_field, fuse):
+        """ValueError where the device-side termination chain does not apply: never a quiet fallback."""
+        if not fuse:
+            raise ValueError("VolumeRenderer.t_stop_count = 'device' needs a net on the single-view fused path")
+        fused = radiance_field.fused()
+        dims = fused.dims(fused._mlp(False))
+        if dims.bn or dims.spade or dims.beta > 0:
+            raise ValueError("VolumeRenderer.t_stop_count = 'device' has counted field kernels for ReLU nets without "
+                             "BatchNorm or use_spade only; use t_stop_count = 'host'")
+
+    def _fine_termination_device(self, ro, rd, z_sorted, radiance_field, grids, SB, R, totals):
+        """Fine pass with early termination and, with grids, empty-space skipping, every count on the device
+        (ops.march_fine_device). totals (SB,) int64: scene b's evaluated fine samples, written by the launches."""
+        Nt = z_sorted.shape[-1]
+        zs = z_sorted.reshape(SB, R, Nt)
+        fused = radiance_field.fused()
+        rgbs, dists = [], []
+        for b in range(SB):
+            def fn(xyz, vd, n_live, b=b):
+                return fused.forward_points_scene_counted(xyz, vd, n_live, False, b)
+            rgb_b, dist_b, _ = ops.march_fine_device(ro[b], rd[b], zs[b], fn, self.t_stop, self.white_back,
+                                                     grid=None if grids is None else grids[b], total=totals[b])
+            rgbs.append(rgb_b)
+            dists.append(dist_b)
+        if SB == 1:
+            return rgbs[0], dists[0]
+        return torch.cat(rgbs, 0), torch.cat(dists, 0)
+
     def _draws(self, SB, R, dev, noise):
         """The reference's RNG draws in its order (renderers.py:14, :41, :45, :63)."""
         if noise is not None:
@@ -234,6 +280,9 @@ class VolumeRenderer(nn.Module):
         Nc, Nt = self.n_coarse, self.n_coarse + self.n_fine
         fuse = hasattr(radiance_field, "can_fuse") and radiance_field.can_fuse(x_pix)
         grids = None if self.occupancy is None else self._occupancy_grids(SB, radiance_field, fuse, dev)
+        stop_on_device = self.t_stop is not None and self.t_stop_count == "device" and not torch.is_grad_enabled()
+        if stop_on_device:
+            self._check_termination_device(radiance_field, fuse)
         draws = self._draws(SB, R, dev, noise)
         seed, off = (self.seed or 0), self._offset
         ids = None
@@ -287,7 +336,17 @@ class VolumeRenderer(nn.Module):
             w_c.detach(), zc, near, far, nf, self.n_fine_depth, self.depth_std,
             u=None if draws is None else draws["u"], u2=None if draws is None else draws["u2"],
             noise_depth=None if draws is None else draws["depth"], seed=seed, offset=off, ray_ids=ids)
-        if self.t_stop is not None and not torch.is_grad_enabled():
+        if stop_on_device:
+            fine = totals[1] if on_device else torch.empty(SB, device=dev, dtype=torch.int64)
+            rgb_f, dist_f = self._fine_termination_device(ro, rd, z_sorted, radiance_field, grids, SB, R, fine)
+            self.last_fine_samples = None
+            self.last_fine_counts = fine[0] if SB == 1 else fine.sum()
+            if on_device:
+                self.last_live_by_pass = self.last_live_samples = None
+                self.last_live_counts = totals[:, 0] if SB == 1 else totals.sum(1)
+            elif grids is not None:   # the coarse pass's host count; the fine pass's stays on the device
+                self.last_live_by_pass, self.last_live_samples = (live[0], None), None
+        elif self.t_stop is not None and not torch.is_grad_enabled():
             rgb_f, dist_f = self._fine_early_termination(ro, rd, z_sorted, radiance_field, fuse, SB, R)
         else:
             ff = field(z_sorted, False)

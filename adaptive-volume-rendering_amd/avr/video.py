@@ -64,7 +64,7 @@ def to_uint8(img):
 
 def render_orbit(renderer, radiance_field, intrinsics, num_frames, radius, height, width=None, fine=True,
                  device=None, t_stop=None, on_frame=None, occupancy=None, occupancy_sigma=0.0, occupancy_box=1.0,
-                 occupancy_count="host"):
+                 occupancy_count="host", t_stop_count="host"):
     """Render num_frames full frames around the orbit with `renderer`
     (e.g. avr.renderers.VolumeRenderer) and a ready radiance field. One
     renderer call per frame (all H * W rays at once), no_grad. Returns
@@ -75,7 +75,16 @@ def render_orbit(renderer, radiance_field, intrinsics, num_frames, radius, heigh
     (avr.occupancy.OccupancyGrid.from_field) and gates every frame; stats then carry
     the live share of the field samples, which is printed at the end.
     occupancy_count = "host" | "device" (renderer.occupancy_count for these frames): with "device" no frame reads
-    its live count back; the counts are summed on the device and read once after the last frame."""
+    its live count back; the counts are summed on the device and read once after the last frame.
+    t_stop_count = "host" | "device" (renderer.t_stop_count for these frames; "device" needs t_stop): with "device"
+    the fine pass is terminated, and with occupancy also gated, without a host read; the evaluated fine samples are
+    summed on the device and read once after the last frame."""
+    if t_stop_count not in ("host", "device"):
+        raise ValueError(f"render_orbit: t_stop_count must be 'host' or 'device', got {t_stop_count!r}")
+    if t_stop is None and t_stop_count != "host":
+        raise ValueError("render_orbit: t_stop_count = 'device' needs t_stop")
+    if occupancy is not None and t_stop is not None and t_stop_count != "device":
+        raise ValueError("render_orbit: occupancy with t_stop needs t_stop_count = 'device'")
     if occupancy_count not in ("host", "device"):
         raise ValueError(f"render_orbit: occupancy_count must be 'host' or 'device', got {occupancy_count!r}")
     if occupancy is None and occupancy_count != "host":
@@ -93,13 +102,17 @@ def render_orbit(renderer, radiance_field, intrinsics, num_frames, radius, heigh
                                         sigma_thr=occupancy_sigma)
     prev = getattr(renderer, "t_stop", None)
     prev_occ = getattr(renderer, "occupancy", None)
+    prev_stop_count = getattr(renderer, "t_stop_count", "host")
     renderer.t_stop = t_stop
+    if t_stop is not None:
+        renderer.t_stop_count = t_stop_count
     prev_count = getattr(renderer, "occupancy_count", "host")
     if grid is not None:
         renderer.occupancy = grid
         renderer.occupancy_count = occupancy_count
     frames, fine_samples, live_samples = [], 0, 0
     live_dev = None   # device mode: the frames' live counts, summed on the device
+    fine_dev = None   # t_stop_count = "device": the frames' evaluated fine samples, likewise
     try:
         torch.cuda.synchronize(device)
         t0 = time.perf_counter()
@@ -107,7 +120,11 @@ def render_orbit(renderer, radiance_field, intrinsics, num_frames, radius, heigh
             for c2w in orbit_cam2world(num_frames, radius):
                 c2w = c2w.to(device).reshape(1, 1, 4, 4).expand(1, n, 4, 4)
                 rgb_c, rgb_f, _, _ = renderer(c2w, K, x_pix, radiance_field)
-                fine_samples += getattr(renderer, "last_fine_samples", 0)
+                if t_stop is not None and t_stop_count == "device":
+                    fine_dev = renderer.last_fine_counts.clone() if fine_dev is None \
+                        else fine_dev + renderer.last_fine_counts
+                else:
+                    fine_samples += getattr(renderer, "last_fine_samples", 0)
                 if grid is not None and occupancy_count == "device":
                     live_dev = renderer.last_live_counts.clone() if live_dev is None \
                         else live_dev + renderer.last_live_counts
@@ -122,11 +139,15 @@ def render_orbit(renderer, radiance_field, intrinsics, num_frames, radius, heigh
         secs = time.perf_counter() - t0
     finally:
         renderer.t_stop = prev
+        if t_stop is not None:
+            renderer.t_stop_count = prev_stop_count
         if grid is not None:
             renderer.occupancy = prev_occ
             renderer.occupancy_count = prev_count
     if live_dev is not None:
         live_samples = int(live_dev.sum().item())   # the one read, after the last frame
+    if fine_dev is not None:
+        fine_samples = int(fine_dev.item())
     stats = {"seconds": secs, "rays_per_s": num_frames * n / secs, "frames": num_frames,
              "rays_per_frame": n, "fine_samples": fine_samples}
     if grid is not None:
@@ -137,13 +158,15 @@ def render_orbit(renderer, radiance_field, intrinsics, num_frames, radius, heigh
     return frames, stats
 
 
-def generate_video(model_input, num_frames, radius, net, model, fine=True, occupancy=None, occupancy_count="host"):
+def generate_video(model_input, num_frames, radius, net, model, fine=True, occupancy=None, occupancy_count="host",
+                   t_stop_count="host"):
     """utils.py:481-537 with the same arguments: encode the first source view
     of model_input into `net`, then render the orbit through `model`
     (a RadFieldAndRenderer). A net whose latent was set with encode_latent()
     keeps it (no `images` needed); otherwise the source view is encoded.
     occupancy = RES, occupancy_count = "host" | "device": render_orbit's empty-space skipping (not in the
-    reference; off by default)."""
+    reference; off by default). t_stop_count = "host" | "device": where render_orbit keeps the counts of the
+    renderer's early termination (model.renderer.t_stop; "device" needs it set)."""
     intrinsics = model_input["intrinsics"][0:1, 0, ...]
     if "images" in model_input and net.encoder.latent.shape[-1] <= 1:   # no latent yet
         gt = model_input["images"]
@@ -152,8 +175,11 @@ def generate_video(model_input, num_frames, radius, net, model, fine=True, occup
         src = gt[0:1, 0:1, ...].reshape(1, -1, sl, sl, 3).permute(0, 1, 4, 2, 3)
         net.encode(src, model_input["cam2world"][0:1, 0:1, ...], model_input["focal"][0, 0], model_input["c"][0, 0, :])
     sl = int(model_input.get("resolution", 0)) or int(np.sqrt(model_input["images"].shape[2]))
+    # (render_orbit sets the renderer's t_stop for its frames: None as before, the renderer's own in device mode)
+    t_stop = getattr(model.renderer, "t_stop", None) if t_stop_count == "device" else None
     frames, stats = render_orbit(model.renderer, net, intrinsics, num_frames, radius, sl, fine=fine,
-                                 occupancy=occupancy, occupancy_count=occupancy_count)
+                                 t_stop=t_stop, occupancy=occupancy,
+                                 occupancy_count=occupancy_count, t_stop_count=t_stop_count)
     print(f"it takes {stats['seconds']} seconds to render a video")
     return frames
 

@@ -763,6 +763,45 @@ int avr_field_fwd_points_counted(const avr_field_dims* dims, const avr_view_desc
                                  const float* table, const float* xyz, const float* viewdirs, int64_t capacity,
                                  const int64_t* n_points, float* out, void* stream);
 
+/* ------------------------------- fine pass, early termination on the device
+ * Additions within ABI 18 (no version change; DESIGN.md "Early termination: device-side chain"): the early
+ * termination of avr_march_* with every count kept on the device, combinable with an occupancy grid. No host read
+ * sizes a launch, nothing is appended with an atomic, so the chain can be recorded in a HIP-graph capture and every
+ * output is bit-reproducible. state is avr_march_init's (its active list is not used). Per chunk [c0, c0 + chunk)
+ * of z (n_rays, n_samples), chunk in 1 .. 64, the number of chunks fixed on the host:
+ *   avr_march_classify -> avr_occ_scan -> avr_march_compact_counted -> avr_field_fwd_points_counted
+ *     -> avr_march_composite_masked
+ * and avr_march_finish after the last chunk.
+ *   avr_march_classify: ray r is ALIVE iff c0 == 0 or (float)state[r].T >= t_stop (avr_march_composite's survivor
+ *     rule: a stopped ray's T is never updated again, so the test needs no flag). A sample of an alive ray is live
+ *     iff it passes avr_occ_classify's test against `grid` (the same point, the same float tests, a non-finite
+ *     coordinate is live); grid == NULL: every sample of an alive ray. -> mask (n_rays) uint64, bit k = sample
+ *     c0 + k is live, bits at or beyond chunk clear, and counts (n_rays) int32. A stopped ray writes mask 0 and
+ *     count 0; every element is written (no memset).
+ *   avr_march_compact_counted: avr_occ_compact_counted for the column window: with offsets and *n_live from
+ *     avr_occ_scan(counts) it writes rows [0, *n_live) of xyz and viewdirs (capacity, 3), ray-major, and nothing
+ *     beyond. capacity <= n_rays * chunk; a device count outside 0 .. capacity is held to that range.
+ *   avr_march_composite_masked: one wave per ray over all n_rays. A stopped ray is left as it is. Otherwise sample
+ *     c0 + k takes row offsets[r] + popcount(mask[r] & ((1 << k) - 1)) of field_c (capacity, 4; 16-B aligned) where
+ *     bit k is set and exactly 0.0f in all four channels where it is clear; from there on the terms, rounding
+ *     points, fp64 scan with the carried T and sums of avr_march_composite, so state is bit-equal to that entry's
+ *     over the same field values. *evaluated (device int64) = *n_live (accumulate == 0) or *evaluated + *n_live
+ *     (accumulate != 0), by a plain load and store of one lane: launches on a stream are ordered.
+ * Checked before any HIP call (AVR_E_INVALID): null pointers, negative n_rays, chunk outside 1 .. 64, c0 < 0 or
+ * c0 + chunk > n_samples, capacity outside 0 .. n_rays * chunk, a grid avr_occ_classify refuses, counts, masks,
+ * offsets or state not 8-B aligned, field rows not 16-B aligned. n_rays == 0 returns AVR_OK with no launch, as does
+ * avr_march_compact_counted with capacity == 0.                                                                  */
+int avr_march_classify(const avr_occ_grid* grid, const float* ro, const float* rd, const float* z, const void* state,
+                       int64_t n_rays, int n_samples, int c0, int chunk, float t_stop, uint64_t* mask,
+                       int32_t* counts, void* stream);
+int avr_march_compact_counted(const float* ro, const float* rd, const float* z, const uint64_t* mask,
+                              const int64_t* offsets, int64_t n_rays, int n_samples, int c0, int chunk,
+                              const int64_t* n_live, int64_t capacity, float* xyz, float* viewdirs, void* stream);
+int avr_march_composite_masked(const float* z, const float* field_c, const uint64_t* mask, const int64_t* offsets,
+                               const int64_t* n_live, int64_t capacity, int64_t n_rays, int n_samples, int c0,
+                               int chunk, float infinity, float t_stop, void* state, int64_t* evaluated,
+                               int accumulate, void* stream);
+
 /* ------------------------------------------------------------ measurement
  * Streaming device copy dst[0, n_bytes) = src[0, n_bytes) (16-B aligned,
  * n_bytes a multiple of 16): the achievable-HBM yardstick bench.py reports
