@@ -238,3 +238,106 @@ def test_bn_training_512_two_scenes_ragged_lin_z():
     _, g_d, _ = _fp64(net, lambda: _grads_bn(net, xyz.double(), vd.double(), w.double(), True, hip=False))
     np.testing.assert_allclose(out_h.cpu().numpy(), out_t.cpu().numpy(), atol=2e-4)
     _compare64(g_h, g_t, g_d, floor=1e-4)
+
+
+def _three_passes(net, xyz, vd, w):
+    """HIP, torch fp32 and torch float64 from the same running statistics -> three (out, gradients, running
+    statistics) triples."""
+    start = _running(net)
+
+    def one(x, v, ww, hip):
+        _set_running(net, start)
+        out, gr, _ = _grads_bn(net, x, v, ww, True, hip=hip)
+        return out, gr, _running(net)
+
+    h = one(xyz, vd, w, True)
+    t = one(xyz, vd, w, False)
+    d = _fp64(net, lambda: one(xyz.double(), vd.double(), w.double(), False))
+    _set_running(net, start)
+    return h, t, d
+
+
+def _compare_passes(what, h, t, d):
+    """_compare64 (2 x torch fp32's error + 1e-4) on the gradients, on the forward, and on the running statistics."""
+    worst_g = _compare64(h[1], t[1], d[1], floor=1e-4)
+    worst_o = _compare64({"out": h[0]}, {"out": t[0]}, {"out": d[0]}, floor=1e-4)
+    stats = [{k: v for k, v in r[2].items() if "num_batches" not in k} for r in (h, t, d)]
+    worst_r = _compare64(*stats, floor=1e-4)
+    for k, v in d[2].items():
+        if "num_batches" in k:
+            assert int(h[2][k]) == int(v), (k, int(h[2][k]), int(v))
+    print(f"{what}: worst HIP error vs float64 (bar: 2 x torch fp32's + 1e-4): gradients {worst_g:.2e} of max |grad|, "
+          f"forward {worst_o:.2e}, running statistics {worst_r:.2e}")
+
+
+def _away_from_relu_thresholds(net, xyz, vd, margin=2e-5, rounds=12):
+    """xyz with the rows nudged (by 1e-4) whose float64 forward of the coarse MLP has a relu input within `margin` of
+    0 -- every bn_0 output, the last block's output and lin_out's sigma, each in units of max(1, its std) -- until
+    there is none; asserts that. fp32 rounding moves these values by ~1e-6 (HIP and torch alike), so no relu mask of
+    either fp32 forward can then differ from float64's. A nudge moves a row's values by ~1e-3 and the batch
+    statistics by 1e-3 / rows, far below the margin, so the loop converges in a few rounds."""
+    mlp = net.mlp_coarse
+    start = _running(net)
+    g = torch.Generator(device="cpu").manual_seed(5)
+    xyz = xyz.clone()
+    M = xyz.shape[0] * xyz.shape[1]
+    for _ in range(rounds):
+        rec = []
+        keep = lambda t: rec.append(t.detach().reshape(M, -1))   # noqa: E731
+        hooks = [blk.bn_0.register_forward_hook(lambda m, i, o: keep(o)) for blk in mlp.blocks]
+        hooks.append(mlp.blocks[-1].register_forward_hook(lambda m, i, o: keep(o)))
+        hooks.append(mlp.lin_out.register_forward_hook(lambda m, i, o: keep(o.reshape(M, -1)[:, 3:])))
+        try:
+            with torch.no_grad():
+                _fp64(net, lambda: net(xyz.double(), coarse=True, viewdirs=vd.double()))
+        finally:
+            for h in hooks:
+                h.remove()
+            _set_running(net, start)
+        assert len(rec) == 2 * len(mlp.blocks) + 2
+        near = torch.stack([(r.abs() / max(1.0, float(r.std()))).min(1).values for r in rec]).min(0).values < margin
+        if not bool(near.any()):
+            return xyz
+        rows = near.reshape(xyz.shape[:2]).nonzero(as_tuple=True)
+        xyz[rows] += 1e-4 * torch.randn(len(rows[0]), 3, generator=g).to(xyz.device)
+    raise AssertionError(f"{int(near.sum())} rows still within {margin} of a relu threshold")
+
+
+def test_bn_training_fold_depth():
+    """33,793 rows: 529 workgroup partials, 34 fold rows -- every wave of the finalize's second stage makes one
+    two-row loop trip and two of them take the tail (every other BN test has at most 2 fold rows) -- and a last
+    workgroup of 1 row. Forward, running statistics and every gradient against float64, _compare64 as it stands.
+
+    At this row count one relu mask that differs from float64's moves a gradient of this net by ~1e-3 of its
+    largest (without one, both fp32 paths are within ~2e-6), and about one of the 6.5 million relu inputs lies
+    within fp32 rounding (~1e-6) of 0: measured with points as drawn, seed 41, HIP flipped 4 masks and torch fp32 3,
+    blocks.0.bn_0.weight HIP 3.0e-3 against torch 6.8e-4; seed 42, the same single flip in both, 6.1e-5 against
+    6.2e-5. That comparison measures which path drew the extra flip, so the points are first moved off the
+    thresholds (_away_from_relu_thresholds): the float64 reference itself then has a margin no fp32 rounding
+    crosses, as the layer tests of test_gpu_bn_kernels.py require of theirs."""
+    net = _bn_net(64, 1)
+    xyz, vd, w = _points(1, 33 * 1024 + 1, seed=41)
+    xyz = _away_from_relu_thresholds(net, xyz, vd)
+    assert net.can_train_bn(xyz, vd)
+    _compare_passes("bn fold depth (64, 1), 33793 rows", *_three_passes(net, xyz, vd, w))
+
+
+def test_bn_training_shifted_statistics():
+    """Pre-BN columns with |mean| / std >> 1 (+20 on every fourth bias of lin_in and of every fc_0) and a constant
+    pre-BN column (a zero row of blocks.0.fc_0.weight: invstd = 1 / sqrt(eps)). Forward, running statistics (also to
+    1e-4 of float64, as test_bn_training_grads_match_fp64 holds them to torch) and every gradient against float64."""
+    net = _bn_net(128, 2)
+    with torch.no_grad():
+        for m in (net.mlp_coarse, net.mlp_fine):
+            m.lin_in.bias[::4] += 20.0
+            for blk in m.blocks:
+                blk.fc_0.bias[::4] += 20.0
+            m.blocks[0].fc_0.weight[1].zero_()
+    xyz, vd, w = _points(1, 700, seed=43)
+    assert net.can_train_bn(xyz, vd)
+    h, t, d = _three_passes(net, xyz, vd, w)
+    _compare_passes("bn shifted statistics (128, 2), 700 rows", h, t, d)
+    for k, b in d[2].items():
+        if "num_batches" not in k:
+            a, b = h[2][k].double(), b.double()
+            assert float((a - b).abs().max()) <= 1e-4 * max(1.0, float(b.abs().max())), k
