@@ -61,13 +61,10 @@ class GraphedRenderer:
     """
 
     def __init__(self, renderer, net, cam2world, intrinsics, x_pix, warmup=2):
-        if renderer.t_stop is not None and getattr(renderer, "t_stop_count", "host") != "device":
-            raise ValueError("GraphedRenderer: early termination sizes its launches on the host (t_stop must be None, "
-                             "or renderer.t_stop_count 'device')")
-        if getattr(renderer, "occupancy", None) is not None and \
-                getattr(renderer, "occupancy_count", "host") != "device":
-            raise ValueError("GraphedRenderer: occupancy gating reads the live count back to the host "
-                             "(renderer.occupancy must be None, or renderer.occupancy_count 'device')")
+        from .renderers import check_skip_modes
+        check_skip_modes("GraphedRenderer: ", renderer.t_stop, getattr(renderer, "t_stop_count", "host"),
+                         getattr(renderer, "occupancy", None), getattr(renderer, "occupancy_count", "host"),
+                         capture=True, name="renderer.{}".format)
         if hasattr(renderer, "stage_host_draws") and renderer.seed is None:
             raise ValueError("GraphedRenderer: the adaptive renderers draw their start distances on the host "
                              "unless seeded (set renderer.seed)")

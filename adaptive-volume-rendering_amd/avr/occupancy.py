@@ -240,15 +240,13 @@ def gated_field(fused, grid, ro, rd, z, coarse, sb=0, count="host", total=None):
     if count not in ("host", "device"):
         raise ValueError(f"gated_field: count must be 'host' or 'device', got {count!r}")
     R, N = z.shape
-    if count == "device":
-        ro = ro.reshape(R, 3).to(F32).contiguous()
-        rd = rd.reshape(R, 3).to(F32).contiguous()
-        return _gated_field_device(fused, grid, ro, rd, z.to(F32).contiguous(), coarse, sb, total)
-    if z.is_cuda and torch.cuda.is_current_stream_capturing():
+    if count == "host" and z.is_cuda and torch.cuda.is_current_stream_capturing():
         raise ValueError("occupancy gating reads the live count back to the host: it cannot be captured in a graph")
     ro = ro.reshape(R, 3).to(F32).contiguous()
     rd = rd.reshape(R, 3).to(F32).contiguous()
     z = z.to(F32).contiguous()
+    if count == "device":
+        return _gated_field_device(fused, grid, ro, rd, z, coarse, sb, total)
     mask, counts = classify(grid, ro, rd, z)
     incl = torch.cumsum(counts, 0, dtype=torch.int64)
     offsets = incl - counts

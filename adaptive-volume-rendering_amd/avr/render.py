@@ -95,17 +95,15 @@ def main(argv=None):
                          "read once after the last frame")
     ap.add_argument("--out", default=None, help="directory for frame_XXX.ppm")
     args = ap.parse_args(argv)
-    if args.t_stop_count is not None and args.t_stop is None:
-        ap.error("--t-stop-count needs --t-stop")
-    t_stop_count = args.t_stop_count or "host"
-    if t_stop_count == "device" and args.renderer != "volume":
-        ap.error("--t-stop-count device needs --renderer volume")
-    if args.occupancy is not None and (args.renderer != "volume"
-                                       or (args.t_stop is not None and t_stop_count != "device")):
-        ap.error("--occupancy needs --renderer volume and no --t-stop (or --t-stop-count device)")
-    if args.occupancy_count is not None and args.occupancy is None:
-        ap.error("--occupancy-count needs --occupancy")
-    occupancy_count = args.occupancy_count or "host"
+    from .renderers import check_skip_modes
+    try:   # the counts as given (None: flag not given), so that a count given without its feature is refused too
+        check_skip_modes("", args.t_stop, args.t_stop_count, args.occupancy, args.occupancy_count, idle=None,
+                         name=lambda n: "--" + n.replace("_", "-"))
+    except ValueError as e:
+        ap.error(str(e))
+    t_stop_count, occupancy_count = args.t_stop_count or "host", args.occupancy_count or "host"
+    if args.renderer != "volume" and (t_stop_count == "device" or args.occupancy is not None):
+        ap.error("--t-stop-count device and --occupancy need --renderer volume")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -122,7 +120,7 @@ def main(argv=None):
     from .parallel import render_sharded
     from .renderers import AdaptiveVolumeRenderer, VolumeRenderer
     from .scene import INTRINSICS
-    from .video import get_opencv_pixel_coordinates, orbit_cam2world, to_uint8, write_ppm
+    from .video import FrameCounts, get_opencv_pixel_coordinates, orbit_cam2world, to_uint8, write_ppm
     load_library()
     net = build_net(args, device)
     if dist is not None:
@@ -168,28 +166,16 @@ def main(argv=None):
     torch.cuda.synchronize()
     if dist is not None:
         dist.barrier()
-    fine_samples = live_samples = 0
-    live_dev = None   # --occupancy-count device: the frames' live counts, summed on the device
-    fine_dev = None   # --t-stop-count device: the frames' evaluated fine samples, likewise
+    counts = FrameCounts(t_stop_count == "device", args.occupancy is not None and occupancy_count == "device")
     t0 = time.perf_counter()
     frames = []
     for c2w in poses:
         rend.last_fine_samples = 0
         _, rgb_f, _, _ = render(c2w)
-        if t_stop_count == "device":
-            fine_dev = rend.last_fine_counts.clone() if fine_dev is None else fine_dev + rend.last_fine_counts
-        else:
-            fine_samples += getattr(rend, "last_fine_samples", 0)
-        if args.occupancy is not None and occupancy_count == "device":
-            live_dev = rend.last_live_counts.clone() if live_dev is None else live_dev + rend.last_live_counts
-        else:
-            live_samples += getattr(rend, "last_live_samples", 0)
+        counts.add(rend)
         frames.append(rgb_f)
     torch.cuda.synchronize()
-    if live_dev is not None:
-        live_samples = int(live_dev.sum().item())   # the one read, after the last frame
-    if fine_dev is not None:
-        fine_samples = int(fine_dev.item())
+    fine_samples, live_samples = counts.read()   # the one read, after the last frame
     if dist is not None:
         dist.barrier()
     secs = time.perf_counter() - t0

@@ -112,6 +112,33 @@ def volume_integral_packed(z_vals, field, white_back=True, infinity=1.8):
 
 
 # ---------------------------------------------------------------- renderer
+_ANY = object()
+
+
+def check_skip_modes(who, t_stop, t_stop_count, occupancy, occupancy_count, idle=_ANY, capture=False, name=str):
+    """What combines of early termination (t_stop, t_stop_count) and occupancy gating (occupancy, occupancy_count),
+    stated once; ValueError otherwise. A count is 'host' or 'device'; occupancy with t_stop needs t_stop_count =
+    'device'; with `idle` given, a count may hold nothing but `idle` while its feature is None (render_orbit: 'host',
+    its default; the CLI: None, a flag not given; left out: the renderer's attributes always hold a mode); with
+    `capture`, the call is to be recorded in a graph, which no host-count mode can be. `who` opens the message and
+    `name` spells the four names in the caller's vocabulary (the CLI: its flags)."""
+    for feature, count, f, c in ((t_stop, t_stop_count, "t_stop", "t_stop_count"),
+                                 (occupancy, occupancy_count, "occupancy", "occupancy_count")):
+        if count not in ("host", "device", idle):
+            raise ValueError(f"{who}{name(c)} must be 'host' or 'device', got {count!r}")
+        if feature is None and idle is not _ANY and count != idle:
+            raise ValueError(f"{who}{name(c)} needs {name(f)}")
+    if capture and t_stop is not None and t_stop_count != "device":
+        raise ValueError(f"{who}early termination sizes its launches on the host: it cannot be captured in a graph "
+                         f"({name('t_stop')} must be None, or {name('t_stop_count')} 'device')")
+    if capture and occupancy is not None and occupancy_count != "device":
+        raise ValueError(f"{who}occupancy gating reads the live count back to the host: it cannot be captured in a "
+                         f"graph ({name('occupancy')} must be None, or {name('occupancy_count')} 'device')")
+    if occupancy is not None and t_stop is not None and t_stop_count != "device":
+        raise ValueError(f"{who}{name('occupancy')} needs {name('t_stop_count')} = 'device' to be combined with "
+                         f"{name('t_stop')} (one chain then terminates and gates the fine pass)")
+
+
 class VolumeRenderer(nn.Module):
     """renderers.py:121-289: coarse stratified pass -> inverse-CDF fine pass
     (+ n_fine_depth 'depth' samples) -> sort -> fine pass -> depth."""
@@ -159,8 +186,7 @@ class VolumeRenderer(nn.Module):
 
     @occupancy_count.setter
     def occupancy_count(self, mode):
-        if mode not in ("host", "device"):
-            raise ValueError(f"VolumeRenderer.occupancy_count must be 'host' or 'device', got {mode!r}")
+        check_skip_modes("VolumeRenderer: ", None, "host", None, mode)
         self._occupancy_count = mode
 
     @property
@@ -169,8 +195,7 @@ class VolumeRenderer(nn.Module):
 
     @t_stop_count.setter
     def t_stop_count(self, mode):
-        if mode not in ("host", "device"):
-            raise ValueError(f"VolumeRenderer.t_stop_count must be 'host' or 'device', got {mode!r}")
+        check_skip_modes("VolumeRenderer: ", None, mode, None, "host")
         self._t_stop_count = mode
 
     def _occupancy_grids(self, SB, radiance_field, fuse, dev):
@@ -180,9 +205,8 @@ class VolumeRenderer(nn.Module):
         grids = list(occ) if isinstance(occ, (list, tuple)) else [occ]
         if torch.is_grad_enabled():
             raise ValueError("VolumeRenderer.occupancy is inference only: call under torch.no_grad()")
-        if self.t_stop is not None and self.t_stop_count != "device":
-            raise ValueError("VolumeRenderer.occupancy cannot be combined with t_stop (t_stop_count = 'device' "
-                             "terminates and gates the fine pass in one chain)")
+        check_skip_modes("VolumeRenderer: ", self.t_stop, self.t_stop_count, occ, self.occupancy_count,
+                         capture=dev.type == "cuda" and torch.cuda.is_current_stream_capturing())
         if len(grids) != SB:
             raise ValueError(f"VolumeRenderer.occupancy holds {len(grids)} grid(s) for {SB} scene(s)")
         if self.n_coarse + self.n_fine > _lib.OCC_MAX_SAMPLES:
@@ -192,9 +216,6 @@ class VolumeRenderer(nn.Module):
         if any(g.stale(radiance_field) for g in grids):
             raise ValueError("VolumeRenderer.occupancy: a grid was built from parameters, a latent map or source "
                              "views that have changed since; rebuild it (OccupancyGrid.from_field)")
-        if self.occupancy_count == "host" and dev.type == "cuda" and torch.cuda.is_current_stream_capturing():
-            raise ValueError("VolumeRenderer.occupancy reads the live count back to the host: it cannot be captured "
-                             "in a graph (occupancy_count = 'device' keeps it on the device)")
         return grids
 
     @classmethod
@@ -204,14 +225,20 @@ class VolumeRenderer(nn.Module):
                    n_fine_depth=conf.get_int("n_fine_depth", 8), depth_std=conf.get_float("depth_std", 0.01),
                    white_back=conf.get_float("white_back", white_back))
 
+    @staticmethod
+    def _fine_per_scene(ro, rd, z_sorted, SB, R, march):
+        """The terminated fine pass, scene by scene: march(b, ro[b], rd[b], z[b]) -> scene b's (rgb, dist, count).
+        -> rgb (SB * R, 3), dist (SB * R,) and the scenes' counts."""
+        zs = z_sorted.reshape(SB, R, z_sorted.shape[-1])
+        outs = [march(b, ro[b], rd[b], zs[b]) for b in range(SB)]
+        rgb, dist = (outs[0][k] if SB == 1 else torch.cat([o[k] for o in outs], 0) for k in (0, 1))
+        return rgb, dist, [o[2] for o in outs]
+
     def _fine_early_termination(self, ro, rd, z_sorted, radiance_field, fuse, SB, R):
         """Fine pass with early ray termination at transmittance < self.t_stop
         (BASELINE config 4, inference only; ops.march_fine)."""
-        Nt = z_sorted.shape[-1]
-        zs = z_sorted.reshape(SB, R, Nt)
-        rgbs, dists, self.last_fine_samples = [], [], 0
-        for b in range(SB):
-            def fn(ro_c, rd_c, z_c, b=b):
+        def march(b, ro_b, rd_b, z_b):
+            def fn(ro_c, rd_c, z_c):
                 if fuse:
                     return radiance_field.fused().forward_rays(ro_c, rd_c, z_c, False, sb=b)
                 pts, vd = ops.points(ro_c, rd_c, z_c)
@@ -219,11 +246,10 @@ class VolumeRenderer(nn.Module):
                 vds = torch.zeros_like(xyz)
                 xyz[b], vds[b] = pts, vd
                 return radiance_field(xyz, viewdirs=vds, coarse=False)[b]
-            rgb_b, dist_b, n = ops.march_fine(ro[b], rd[b], zs[b], fn, self.t_stop, self.white_back)
-            rgbs.append(rgb_b)
-            dists.append(dist_b)
-            self.last_fine_samples += n
-        return torch.cat(rgbs, 0), torch.cat(dists, 0)
+            return ops.march_fine(ro_b, rd_b, z_b, fn, self.t_stop, self.white_back)
+        rgb, dist, counts = self._fine_per_scene(ro, rd, z_sorted, SB, R, march)
+        self.last_fine_samples = sum(counts)
+        return rgb, dist
 
     def _check_termination_device(self, radiance_field, fuse):
         """ValueError where the device-side termination chain does not apply: never a quiet fallback."""
@@ -238,20 +264,32 @@ class VolumeRenderer(nn.Module):
     def _fine_termination_device(self, ro, rd, z_sorted, radiance_field, grids, SB, R, totals):
         """Fine pass with early termination and, with grids, empty-space skipping, every count on the device
         (ops.march_fine_device). totals (SB,) int64: scene b's evaluated fine samples, written by the launches."""
-        Nt = z_sorted.shape[-1]
-        zs = z_sorted.reshape(SB, R, Nt)
         fused = radiance_field.fused()
-        rgbs, dists = [], []
-        for b in range(SB):
-            def fn(xyz, vd, n_live, b=b):
+
+        def march(b, ro_b, rd_b, z_b):
+            def fn(xyz, vd, n_live):
                 return fused.forward_points_scene_counted(xyz, vd, n_live, False, b)
-            rgb_b, dist_b, _ = ops.march_fine_device(ro[b], rd[b], zs[b], fn, self.t_stop, self.white_back,
-                                                     grid=None if grids is None else grids[b], total=totals[b])
-            rgbs.append(rgb_b)
-            dists.append(dist_b)
-        if SB == 1:
-            return rgbs[0], dists[0]
-        return torch.cat(rgbs, 0), torch.cat(dists, 0)
+            return ops.march_fine_device(ro_b, rd_b, z_b, fn, self.t_stop, self.white_back,
+                                         grid=None if grids is None else grids[b], total=totals[b])
+        return self._fine_per_scene(ro, rd, z_sorted, SB, R, march)[:2]
+
+    def _record_counts(self, grids, on_device, stop_on_device, live, totals, fine):
+        """The five last_* attributes after a call. live: the gated passes' host counts, in pass order; totals (2, SB)
+        the device-count passes' live samples per pass and scene; fine: the fine samples that reached the field -- an
+        int (None: _fine_early_termination has set it), or (SB,) int64 on the device when the chain kept it there.
+        Host numbers where the mode has them, None where they would need a sync; an ungated call leaves the live
+        counters as they were."""
+        if stop_on_device:
+            self.last_fine_samples, self.last_fine_counts = None, fine[0] if fine.shape[0] == 1 else fine.sum()
+        elif fine is not None:
+            self.last_fine_samples = fine
+        if on_device:
+            self.last_live_by_pass = self.last_live_samples = None
+            self.last_live_counts = totals[:, 0] if totals.shape[1] == 1 else totals.sum(1)
+        elif grids is not None and stop_on_device:   # the coarse pass's host count; the fine pass's is on the device
+            self.last_live_by_pass, self.last_live_samples = (live[0], None), None
+        elif grids is not None and fine is not None:
+            self.last_live_by_pass, self.last_live_samples = tuple(live), sum(live)
 
     def _draws(self, SB, R, dev, noise):
         """The reference's RNG draws in its order (renderers.py:14, :41, :45, :63)."""
@@ -307,18 +345,14 @@ class VolumeRenderer(nn.Module):
 
         def field(z, coarse):
             n = z.shape[-1]
-            if on_device:
-                from .occupancy import gated_field
-                fusedf = radiance_field.fused()
-                outs = [gated_field(fusedf, grids[b], ro[b], rd[b], z[b * R:(b + 1) * R], coarse, sb=b, count="device",
-                                    total=totals[0 if coarse else 1, b])[0] for b in range(SB)]
-                return (outs[0] if SB == 1 else torch.cat(outs, 0)).reshape(SB * R, n, 4)
             if grids is not None:   # per scene: the field on the live samples only, exact zeros elsewhere
                 from .occupancy import gated_field
                 fusedf = radiance_field.fused()
-                outs = [gated_field(fusedf, grids[b], ro[b], rd[b], z[b * R:(b + 1) * R], coarse, sb=b)
-                        for b in range(SB)]
-                live.append(sum(m for _, m in outs))
+                outs = [gated_field(fusedf, grids[b], ro[b], rd[b], z[b * R:(b + 1) * R], coarse, sb=b,
+                                    count=self.occupancy_count,
+                                    total=totals[0 if coarse else 1, b] if on_device else None) for b in range(SB)]
+                if not on_device:
+                    live.append(sum(m for _, m in outs))
                 out = outs[0][0] if SB == 1 else torch.cat([f for f, _ in outs], 0)
                 return out.reshape(SB * R, n, 4)
             if fuse:
@@ -339,30 +373,20 @@ class VolumeRenderer(nn.Module):
         if stop_on_device:
             fine = totals[1] if on_device else torch.empty(SB, device=dev, dtype=torch.int64)
             rgb_f, dist_f = self._fine_termination_device(ro, rd, z_sorted, radiance_field, grids, SB, R, fine)
-            self.last_fine_samples = None
-            self.last_fine_counts = fine[0] if SB == 1 else fine.sum()
-            if on_device:
-                self.last_live_by_pass = self.last_live_samples = None
-                self.last_live_counts = totals[:, 0] if SB == 1 else totals.sum(1)
-            elif grids is not None:   # the coarse pass's host count; the fine pass's stays on the device
-                self.last_live_by_pass, self.last_live_samples = (live[0], None), None
         elif self.t_stop is not None and not torch.is_grad_enabled():
+            fine = None
             rgb_f, dist_f = self._fine_early_termination(ro, rd, z_sorted, radiance_field, fuse, SB, R)
         else:
+            fine = z_sorted.numel()
             ff = field(z_sorted, False)
-            self.last_fine_samples = z_sorted.numel()
-            if on_device:
-                self.last_live_by_pass = self.last_live_samples = None
-                self.last_live_counts = totals[:, 0] if SB == 1 else totals.sum(1)
-            elif grids is not None:
-                self.last_live_by_pass, self.last_live_samples = tuple(live), sum(live)
             if fast_depth:
                 # the fine weights are not returned (renderers.py:264-277): no store without autograd
                 rgb_f, dist_f, _, depth = ops.composite_depth(z_sorted, ff, ro, rd, depth_row, self.white_back)
-                depth = depth.reshape(SB, R)
-                return rgb_c.reshape(SB, R, 3), rgb_f.reshape(SB, R, 3), depth, depth
-            rgb_f, dist_f, _ = ops.composite(z_sorted, ff, self.white_back, want_weights=False)
-        depth = ops.depth_from_world(ro, rd, dist_f.reshape(SB, R), c2w_info)
+            else:
+                rgb_f, dist_f, _ = ops.composite(z_sorted, ff, self.white_back, want_weights=False)
+        self._record_counts(grids, on_device, stop_on_device, live, totals, fine)
+        # (fast_depth: no termination, so the full pass above and its epilogue's depth)
+        depth = depth.reshape(SB, R) if fast_depth else ops.depth_from_world(ro, rd, dist_f.reshape(SB, R), c2w_info)
         assert z_sorted.shape[-1] == Nt
         return rgb_c.reshape(SB, R, 3), rgb_f.reshape(SB, R, 3), depth, depth
 

@@ -6,6 +6,7 @@ and can terminate the fine pass early (BASELINE config 4).
 
 Frames come back as uint8 (H, W, 3) numpy arrays like the reference's;
 `write_ppm` stores them without an image library."""
+import contextlib
 import math
 import time
 
@@ -62,6 +63,37 @@ def to_uint8(img):
     return np.clip(img * 255, 0, 255).astype(np.uint8)
 
 
+@contextlib.contextmanager
+def renderer_modes(renderer, **modes):
+    """renderer.NAME = value for every NAME=value while the block runs, the former values after it (a renderer without
+    such an attribute is left with the attribute's default: None, or 'host' for a count)."""
+    prev = {k: getattr(renderer, k, "host" if k.endswith("_count") else None) for k in modes}
+    try:
+        for k, v in modes.items():
+            setattr(renderer, k, v)
+        yield
+    finally:
+        for k, v in prev.items():
+            setattr(renderer, k, v)
+
+
+class FrameCounts:
+    """The field samples a renderer evaluated over a run of frames, fine and live. A count the renderer keeps on the
+    device (t_stop_count / occupancy_count = 'device') is summed there frame by frame; read() -> (fine, live) as ints
+    reads those sums, once, after the last frame."""
+
+    def __init__(self, fine_on_device, live_on_device):
+        self._attrs = ("last_fine_counts" if fine_on_device else "last_fine_samples",
+                       "last_live_counts" if live_on_device else "last_live_samples")
+        self._sums = [0, 0]
+
+    def add(self, renderer):   # (0 + a device tensor is a new tensor: a captured graph's buffer is not kept)
+        self._sums = [s + getattr(renderer, a, 0) for s, a in zip(self._sums, self._attrs)]
+
+    def read(self):
+        return tuple(int(s.sum().item()) if torch.is_tensor(s) else s for s in self._sums)
+
+
 def render_orbit(renderer, radiance_field, intrinsics, num_frames, radius, height, width=None, fine=True,
                  device=None, t_stop=None, on_frame=None, occupancy=None, occupancy_sigma=0.0, occupancy_box=1.0,
                  occupancy_count="host", t_stop_count="host"):
@@ -79,16 +111,8 @@ def render_orbit(renderer, radiance_field, intrinsics, num_frames, radius, heigh
     t_stop_count = "host" | "device" (renderer.t_stop_count for these frames; "device" needs t_stop): with "device"
     the fine pass is terminated, and with occupancy also gated, without a host read; the evaluated fine samples are
     summed on the device and read once after the last frame."""
-    if t_stop_count not in ("host", "device"):
-        raise ValueError(f"render_orbit: t_stop_count must be 'host' or 'device', got {t_stop_count!r}")
-    if t_stop is None and t_stop_count != "host":
-        raise ValueError("render_orbit: t_stop_count = 'device' needs t_stop")
-    if occupancy is not None and t_stop is not None and t_stop_count != "device":
-        raise ValueError("render_orbit: occupancy with t_stop needs t_stop_count = 'device'")
-    if occupancy_count not in ("host", "device"):
-        raise ValueError(f"render_orbit: occupancy_count must be 'host' or 'device', got {occupancy_count!r}")
-    if occupancy is None and occupancy_count != "host":
-        raise ValueError("render_orbit: occupancy_count = 'device' needs occupancy = RES")
+    from .renderers import check_skip_modes
+    check_skip_modes("render_orbit: ", t_stop, t_stop_count, occupancy, occupancy_count, idle="host")
     width = width or height
     device = device or intrinsics.device
     K = intrinsics.reshape(1, 3, 3).to(device)
@@ -100,36 +124,22 @@ def render_orbit(renderer, radiance_field, intrinsics, num_frames, radius, heigh
         h = float(occupancy_box)
         grid = OccupancyGrid.from_field(radiance_field, (-h, -h, -h), (h, h, h), (int(occupancy),) * 3,
                                         sigma_thr=occupancy_sigma)
-    prev = getattr(renderer, "t_stop", None)
-    prev_occ = getattr(renderer, "occupancy", None)
-    prev_stop_count = getattr(renderer, "t_stop_count", "host")
-    renderer.t_stop = t_stop
+    modes = {"t_stop": t_stop}
     if t_stop is not None:
-        renderer.t_stop_count = t_stop_count
-    prev_count = getattr(renderer, "occupancy_count", "host")
+        modes["t_stop_count"] = t_stop_count
     if grid is not None:
-        renderer.occupancy = grid
-        renderer.occupancy_count = occupancy_count
-    frames, fine_samples, live_samples = [], 0, 0
-    live_dev = None   # device mode: the frames' live counts, summed on the device
-    fine_dev = None   # t_stop_count = "device": the frames' evaluated fine samples, likewise
-    try:
+        modes.update(occupancy=grid, occupancy_count=occupancy_count)
+    frames = []
+    counts = FrameCounts(t_stop is not None and t_stop_count == "device",
+                         grid is not None and occupancy_count == "device")
+    with renderer_modes(renderer, **modes):
         torch.cuda.synchronize(device)
         t0 = time.perf_counter()
         with torch.no_grad():
             for c2w in orbit_cam2world(num_frames, radius):
                 c2w = c2w.to(device).reshape(1, 1, 4, 4).expand(1, n, 4, 4)
                 rgb_c, rgb_f, _, _ = renderer(c2w, K, x_pix, radiance_field)
-                if t_stop is not None and t_stop_count == "device":
-                    fine_dev = renderer.last_fine_counts.clone() if fine_dev is None \
-                        else fine_dev + renderer.last_fine_counts
-                else:
-                    fine_samples += getattr(renderer, "last_fine_samples", 0)
-                if grid is not None and occupancy_count == "device":
-                    live_dev = renderer.last_live_counts.clone() if live_dev is None \
-                        else live_dev + renderer.last_live_counts
-                else:
-                    live_samples += getattr(renderer, "last_live_samples", 0)
+                counts.add(renderer)
                 img = (rgb_f if fine else rgb_c)[0].reshape(height, width, 3)
                 frame = to_uint8(img.float().cpu().numpy())
                 frames.append(frame)
@@ -137,17 +147,7 @@ def render_orbit(renderer, radiance_field, intrinsics, num_frames, radius, heigh
                     on_frame(len(frames) - 1, frame)
         torch.cuda.synchronize(device)
         secs = time.perf_counter() - t0
-    finally:
-        renderer.t_stop = prev
-        if t_stop is not None:
-            renderer.t_stop_count = prev_stop_count
-        if grid is not None:
-            renderer.occupancy = prev_occ
-            renderer.occupancy_count = prev_count
-    if live_dev is not None:
-        live_samples = int(live_dev.sum().item())   # the one read, after the last frame
-    if fine_dev is not None:
-        fine_samples = int(fine_dev.item())
+    fine_samples, live_samples = counts.read()
     stats = {"seconds": secs, "rays_per_s": num_frames * n / secs, "frames": num_frames,
              "rays_per_frame": n, "fine_samples": fine_samples}
     if grid is not None:

@@ -7,7 +7,7 @@
 // scan in fp64 with a carry between rounds (the reference's ATen cumprod also
 // accumulates in fp64) and is rounded to fp32 before w = a * T, exactly as the
 // reference does. The white-background sum uses the torch-CPU cascade order.
-#include "avr_common.h"
+#include "skip_common.h"   // sample_terms
 
 namespace avr {
 
@@ -38,24 +38,6 @@ __device__ float cascade_sum_wave_c(const float* x, int N, int lane, float* scra
   __builtin_amdgcn_wave_barrier();
   __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
   return scratch[40];
-}
-
-struct SampleTerms {
-  float d, e, alpha, t, zz;
-};
-
-__device__ __forceinline__ SampleTerms sample_terms(const float* __restrict__ zr, int n, int N, float sigma,
-                                                    float infinity) {
-  SampleTerms s;
-  const float z0 = zr[n];
-  const bool last = (n == N - 1);
-  const float z1 = last ? 0.f : zr[n + 1];
-  s.d = last ? 1e10f : fsub(z1, z0);
-  s.zz = last ? infinity : z1;
-  s.e = expf(-fmul(sigma, s.d));
-  s.alpha = fsub(1.0f, s.e);
-  s.t = fadd(fsub(1.0f, s.alpha), 1e-10f);
-  return s;
 }
 
 // Forward: lane l owns the K consecutive samples [K l, K l + K) of its ray

@@ -16,15 +16,13 @@
 //   march_composite one wave per active ray: terms, fp64 product scan with
 //                   carry T, sums; survivors appended to the next active list
 //   march_finish    rgb (+ white background 1 - sum w), distance
-#include "avr_common.h"
+// MarchState and the composite of one chunk (chunk_composite) are skip_common.h's, shared with march_device.hip,
+// whose chain keeps every count on the device.
+#include "skip_common.h"
 
 namespace avr {
 
 constexpr int kMarchWaves = 4;
-
-struct MarchState {  // per ray, fp64
-  double T, r, g, b, d, w;
-};
 
 __global__ void march_init_kernel(int64_t n_rays, MarchState* __restrict__ st, int32_t* __restrict__ active) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -61,32 +59,11 @@ __global__ void __launch_bounds__(64 * kMarchWaves) march_composite_kernel(
   const int n = c0 + lane;
   const bool ok = lane < C;
   float4 f = ok ? field[a * C + lane] : make_float4(0.f, 0.f, 0.f, 0.f);
-  float alpha = 0.f, t = 1.f, zz = 0.f;
-  if (ok) {  // same terms and rounding points as composite_fwd_kernel (renderers.py:79-111)
-    const bool last = n == N - 1;
-    const float z0 = zr[n];
-    const float z1 = last ? 0.f : zr[n + 1];
-    const float d = last ? 1e10f : fsub(z1, z0);
-    zz = last ? infinity : z1;
-    alpha = fsub(1.0f, expf(-fmul(f.w, d)));
-    t = fadd(fsub(1.0f, alpha), 1e-10f);
-  }
   MarchState s = st[ray];
-  const double incl = wave_incl_scan_mul((double)t, lane) * s.T;
-  double excl = __shfl_up(incl, 1, 64);
-  if (lane == 0) excl = s.T;
-  const double Tn = __shfl(incl, 63, 64);
-  const float w = fmul(alpha, (float)excl);
-  const double r = wave_sum_d(ok ? (double)w * f.x : 0.0);
-  const double g = wave_sum_d(ok ? (double)w * f.y : 0.0);
-  const double b = wave_sum_d(ok ? (double)w * f.z : 0.0);
-  const double dd = wave_sum_d(ok ? (double)w * zz : 0.0);
-  const double ws = wave_sum_d(ok ? (double)w : 0.0);
+  chunk_composite(f, ok, zr, n, N, infinity, lane, s);
   if (lane == 0) {
-    s.T = Tn;
-    s.r += r; s.g += g; s.b += b; s.d += dd; s.w += ws;
     st[ray] = s;
-    if (c0 + C < N && (float)Tn >= t_stop) next[atomicAdd(n_next, 1)] = (int32_t)ray;
+    if (c0 + C < N && (float)s.T >= t_stop) next[atomicAdd(n_next, 1)] = (int32_t)ray;
   }
 }
 
@@ -124,12 +101,17 @@ extern "C" int avr_march_init(int64_t n_rays, void* state, int32_t* active, void
   return check_launch("march_init_kernel");
 }
 
+static int march_sizes(const char* who, int64_t n_act, int n_samples, int c0, int chunk) {
+  AVR_REQUIRE(n_act >= 0 && n_samples > 0 && chunk > 0 && chunk <= 64 && c0 >= 0 && c0 + chunk <= n_samples,
+              "%s: bad sizes (n_act %lld, N %d, c0 %d, C %d)", who, (long long)n_act, n_samples, c0, chunk);
+  return AVR_OK;
+}
+
 extern "C" int avr_march_gather(const float* ro, const float* rd, const float* z, const int32_t* active,
                                 int64_t n_act, int n_samples, int c0, int chunk, float* ro_c, float* rd_c, float* z_c,
                                 void* stream) {
-  AVR_REQUIRE(n_act >= 0 && n_samples > 0 && chunk > 0 && chunk <= 64 && c0 >= 0 && c0 + chunk <= n_samples,
-              "march_gather: bad sizes (n_act %lld, N %d, c0 %d, C %d)", (long long)n_act, n_samples, c0, chunk);
-  if (n_act == 0) return AVR_OK;
+  const int rc = march_sizes("march_gather", n_act, n_samples, c0, chunk);
+  if (rc || n_act == 0) return rc;
   AVR_REQUIRE(ro && rd && z && active && ro_c && rd_c && z_c, "march_gather: null pointer");
   march_gather_kernel<<<(unsigned)((n_act + 3) / 4), 256, 0, as_stream(stream)>>>(ro, rd, z, active, n_act,
                                                                                  n_samples, c0, chunk, ro_c, rd_c,
@@ -140,9 +122,8 @@ extern "C" int avr_march_gather(const float* ro, const float* rd, const float* z
 extern "C" int avr_march_composite(const float* z, const float* field_c, const int32_t* active, int64_t n_act,
                                    int n_samples, int c0, int chunk, float infinity, float t_stop, void* state,
                                    int32_t* active_next, int32_t* n_next, void* stream) {
-  AVR_REQUIRE(n_act >= 0 && n_samples > 0 && chunk > 0 && chunk <= 64 && c0 >= 0 && c0 + chunk <= n_samples,
-              "march_composite: bad sizes (n_act %lld, N %d, c0 %d, C %d)", (long long)n_act, n_samples, c0, chunk);
-  if (n_act == 0) return AVR_OK;
+  const int rc = march_sizes("march_composite", n_act, n_samples, c0, chunk);
+  if (rc || n_act == 0) return rc;
   AVR_REQUIRE(z && field_c && active && state && active_next && n_next, "march_composite: null pointer");
   march_composite_kernel<<<(unsigned)((n_act + kMarchWaves - 1) / kMarchWaves), 64 * kMarchWaves, 0,
                            as_stream(stream)>>>(z, reinterpret_cast<const float4*>(field_c), active, n_act,

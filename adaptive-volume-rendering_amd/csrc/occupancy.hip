@@ -16,35 +16,14 @@
 // array, no atomics, no data-dependent order, so every output is bit-reproducible. The point is formed with the
 // operations of field_common.h's sample_geom (fadd(ro, fmul(rd, z))), so a compacted point is the point
 // avr_field_fwd_rays would have formed, bit for bit. All four are bandwidth-trivial next to the field kernel; the
-// grid (at most 2 Mbit) stays in L2.
-#include "avr_common.h"
+// grid (at most 2 Mbit) stays in L2. The grid, the live test, the rank, the point and the clamped device count are
+// skip_common.h's, shared with march_device.hip.
+#include "skip_common.h"
 
 namespace avr {
 
 constexpr int kOccThreads = 256;
 constexpr int kOccRaysPerBlock = kOccThreads / kWave;
-
-struct OccGrid {
-  float lo[3], inv[3];
-  int res[3];
-  const uint32_t* bits;
-};
-
-// The live test of include/avr.h: the float comparisons 0 <= t < res are the integer test on floorf(t) for every
-// finite t and stay defined for an infinite one (a finite point far outside the box: dead).
-__device__ __forceinline__ bool occ_live(const OccGrid& g, float p0, float p1, float p2) {
-  if (!(isfinite(p0) && isfinite(p1) && isfinite(p2))) return true;   // the field sees it, as in the ungated render
-  const float t0 = fmul(fsub(p0, g.lo[0]), g.inv[0]);
-  const float t1 = fmul(fsub(p1, g.lo[1]), g.inv[1]);
-  const float t2 = fmul(fsub(p2, g.lo[2]), g.inv[2]);
-  if (!(t0 >= 0.f && t0 < (float)g.res[0] && t1 >= 0.f && t1 < (float)g.res[1] && t2 >= 0.f && t2 < (float)g.res[2]))
-    return false;
-  const int ix = (int)floorf(t0), iy = (int)floorf(t1), iz = (int)floorf(t2);
-  const int word = (iz * g.res[1] + iy) * (g.res[0] >> 5) + (ix >> 5);
-  return (g.bits[word] >> (ix & 31)) & 1u;
-}
-
-__device__ __forceinline__ int lane_rank(uint64_t m, int lane) { return __popcll(m & ((1ull << lane) - 1ull)); }
 
 __global__ void __launch_bounds__(kOccThreads) occ_build_kernel(const float* __restrict__ sigma, int n_planes, int rx,
                                                                  int ry, int rz, float thr, int dilate,
@@ -78,15 +57,13 @@ __global__ void __launch_bounds__(kOccThreads) occ_classify_kernel(OccGrid g, co
   if (r >= n_rays) return;   // whole waves leave together
   const int lane = threadIdx.x & (kWave - 1);
   const int n_words = (n_samples + kWave - 1) / kWave;
-  const float o0 = ro[3 * r], o1 = ro[3 * r + 1], o2 = ro[3 * r + 2];
-  const float d0 = rd[3 * r], d1 = rd[3 * r + 1], d2 = rd[3 * r + 2];
   int count = 0;
   for (int w = 0; w < n_words; ++w) {
     const int s = w * kWave + lane;
     bool live = false;
     if (s < n_samples) {
-      const float zz = z[r * n_samples + s];
-      live = occ_live(g, fadd(o0, fmul(d0, zz)), fadd(o1, fmul(d1, zz)), fadd(o2, fmul(d2, zz)));
+      const Point3 p = sample_point(ro, rd, r, z[r * n_samples + s]);
+      live = occ_live(g, p.x, p.y, p.z);
     }
     const uint64_t m = __ballot(live);
     if (lane == 0) mask[r * n_words + w] = m;
@@ -103,7 +80,6 @@ __device__ __forceinline__ void occ_compact_body(const float* __restrict__ ro, c
   if (r >= n_rays) return;
   const int lane = threadIdx.x & (kWave - 1);
   const int n_words = (n_samples + kWave - 1) / kWave;
-  const float o0 = ro[3 * r], o1 = ro[3 * r + 1], o2 = ro[3 * r + 2];
   const float d0 = rd[3 * r], d1 = rd[3 * r + 1], d2 = rd[3 * r + 2];
   int64_t base = offsets[r];
   for (int w = 0; w < n_words; ++w) {
@@ -113,10 +89,8 @@ __device__ __forceinline__ void occ_compact_body(const float* __restrict__ ro, c
     // s < n_samples and 0 <= q < n_live hold for the mask and offsets of avr_occ_classify; checked so that
     // inconsistent arguments cannot write outside xyz / viewdirs
     if (((m >> lane) & 1ull) && s < n_samples && q >= 0 && q < n_live) {
-      const float zz = z[r * n_samples + s];
-      xyz[3 * q] = fadd(o0, fmul(d0, zz));
-      xyz[3 * q + 1] = fadd(o1, fmul(d1, zz));
-      xyz[3 * q + 2] = fadd(o2, fmul(d2, zz));
+      const Point3 p = sample_point(ro, rd, r, z[r * n_samples + s]);
+      xyz[3 * q] = p.x; xyz[3 * q + 1] = p.y; xyz[3 * q + 2] = p.z;
       vd[3 * q] = d0; vd[3 * q + 1] = d1; vd[3 * q + 2] = d2;
     }
     base += __popcll(m);
@@ -131,13 +105,6 @@ __global__ void __launch_bounds__(kOccThreads) occ_compact_kernel(const float* _
                                                                    int n_samples, int64_t n_live,
                                                                    float* __restrict__ xyz, float* __restrict__ vd) {
   occ_compact_body(ro, rd, z, mask, offsets, n_rays, n_samples, n_live, xyz, vd);
-}
-
-// The live count of the *_counted kernels: *n_live on the device, held to 0 .. capacity (what xyz, viewdirs and
-// field_c were sized for), so q < *n_live and q < capacity are one test.
-__device__ __forceinline__ int64_t counted_live(const int64_t* __restrict__ n_live, int64_t capacity) {
-  const int64_t n = *n_live;
-  return n < 0 ? 0 : (n < capacity ? n : capacity);
 }
 
 __global__ void __launch_bounds__(kOccThreads) occ_compact_counted_kernel(
@@ -292,15 +259,6 @@ static int occ_rays(const char* who, int64_t n_rays, int n_samples, int64_t* blo
   return AVR_OK;
 }
 
-static int occ_res(const char* who, const int* res) {
-  AVR_REQUIRE(res, "%s: null res", who);
-  for (int a = 0; a < 3; ++a)
-    AVR_REQUIRE(res[a] >= 1 && res[a] <= AVR_OCC_MAX_RES, "%s: res[%d] = %d outside 1..%d", who, a, res[a],
-                AVR_OCC_MAX_RES);
-  AVR_REQUIRE(res[0] % 32 == 0, "%s: res[0] = %d is not a multiple of 32", who, res[0]);
-  return AVR_OK;
-}
-
 extern "C" int avr_occ_build(const float* sigma, int n_planes, const int* res, float thr, int dilate, uint32_t* bits,
                              void* stream) {
   int rc = occ_res("avr_occ_build", res);
@@ -316,16 +274,12 @@ extern "C" int avr_occ_build(const float* sigma, int n_planes, const int* res, f
 
 extern "C" int avr_occ_classify(const avr_occ_grid* grid, const float* ro, const float* rd, const float* z,
                                 int64_t n_rays, int n_samples, uint64_t* mask, int32_t* counts, void* stream) {
-  AVR_REQUIRE(grid, "avr_occ_classify: null grid");
   int64_t blocks;
-  int rc = occ_res("avr_occ_classify", grid->res);
+  OccGrid g;
+  int rc = occ_grid_arg("avr_occ_classify", grid, false, &g);
   if (rc || (rc = occ_rays("avr_occ_classify", n_rays, n_samples, &blocks))) return rc;
-  AVR_REQUIRE(grid->bits, "avr_occ_classify: null grid bits");
   if (n_rays == 0) return AVR_OK;
   AVR_REQUIRE(ro && rd && z && mask && counts, "avr_occ_classify: null pointer");
-  OccGrid g;
-  for (int a = 0; a < 3; ++a) { g.lo[a] = grid->lo[a]; g.inv[a] = grid->inv[a]; g.res[a] = grid->res[a]; }
-  g.bits = grid->bits;
   occ_classify_kernel<<<(unsigned)blocks, kOccThreads, 0, as_stream(stream)>>>(g, ro, rd, z, n_rays, n_samples, mask,
                                                                               counts);
   return check_launch("occ_classify_kernel");
@@ -389,18 +343,12 @@ extern "C" int avr_occ_scan(const int32_t* counts, int64_t n_rays, int64_t* offs
   return check_launch("occ_scan_block_kernel");
 }
 
-static int occ_capacity(const char* who, int64_t capacity, int64_t n_rays, int n_samples) {
-  AVR_REQUIRE(capacity >= 0 && capacity <= n_rays * n_samples, "%s: capacity %lld outside 0..n_rays * n_samples", who,
-              (long long)capacity);
-  return AVR_OK;
-}
-
 extern "C" int avr_occ_compact_counted(const float* ro, const float* rd, const float* z, const uint64_t* mask,
                                        const int64_t* offsets, int64_t n_rays, int n_samples, const int64_t* n_live,
                                        int64_t capacity, float* xyz, float* viewdirs, void* stream) {
   int64_t blocks;
   int rc = occ_rays("avr_occ_compact_counted", n_rays, n_samples, &blocks);
-  if (rc || (rc = occ_capacity("avr_occ_compact_counted", capacity, n_rays, n_samples))) return rc;
+  if (rc || (rc = counted_capacity("avr_occ_compact_counted", capacity, n_rays, n_samples, "n_samples"))) return rc;
   if (n_rays == 0 || capacity == 0) return AVR_OK;
   AVR_REQUIRE(ro && rd && z && mask && offsets && n_live && xyz && viewdirs, "avr_occ_compact_counted: null pointer");
   AVR_REQUIRE(((uintptr_t)n_live & 7) == 0, "avr_occ_compact_counted: n_live must be 8-B aligned");
@@ -414,7 +362,7 @@ extern "C" int avr_occ_expand_counted(const float* field_c, const uint64_t* mask
                                       float* field, void* stream) {
   int64_t blocks;
   int rc = occ_rays("avr_occ_expand_counted", n_rays, n_samples, &blocks);
-  if (rc || (rc = occ_capacity("avr_occ_expand_counted", capacity, n_rays, n_samples))) return rc;
+  if (rc || (rc = counted_capacity("avr_occ_expand_counted", capacity, n_rays, n_samples, "n_samples"))) return rc;
   if (n_rays == 0 || capacity == 0) return AVR_OK;
   AVR_REQUIRE(field_c && mask && offsets && n_live && field, "avr_occ_expand_counted: null pointer");
   AVR_REQUIRE(((uintptr_t)n_live & 7) == 0, "avr_occ_expand_counted: n_live must be 8-B aligned");

@@ -9,20 +9,7 @@
 #include <stdlib.h>
 #include <string.h>
 
-#include "avr.h"
-
-static int failures = 0;
-
-static void expect(const char* what, int got, int want, const char* needle) {
-  const char* msg = avr_last_error_string();
-  if (got != want) {
-    fprintf(stderr, "FAIL %s: got %d want %d (%s)\n", what, got, want, msg);
-    ++failures;
-  } else if (want != AVR_OK && (strlen(msg) == 0 || (needle && !strstr(msg, needle)))) {
-    fprintf(stderr, "FAIL %s: error string '%s' lacks '%s'\n", what, msg, needle ? needle : "any text");
-    ++failures;
-  }
-}
+#include "abi_check_common.h"
 
 /* the call's arguments, so that each check changes one of them */
 typedef struct {
