@@ -228,6 +228,12 @@ _SIGS = {
                                   i64, c_void_p, c_void_p, c_void_p],
     "avr_march_composite_masked": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, i64, i64, c_int, c_int, c_int,
                                    c_float, c_float, c_void_p, c_void_p, c_int, c_void_p],
+    "avr_occ_children": [ctypes.POINTER(OccGrid), c_int, ctypes.POINTER(c_int), c_void_p, c_void_p, c_void_p],
+    "avr_occ_child_points": [c_void_p, c_void_p, ctypes.POINTER(c_int), ctypes.POINTER(ctypes.c_double),
+                             ctypes.POINTER(ctypes.c_double), c_float_p, i64, c_void_p, c_void_p, c_void_p],
+    "avr_occ_flag_sigma": [c_void_p, c_float, c_int, i64, c_void_p, c_void_p],
+    "avr_occ_build_sparse": [c_void_p, c_void_p, c_void_p, i64, ctypes.POINTER(c_int), c_int, c_void_p, c_void_p],
+    "avr_occ_downsample": [c_void_p, ctypes.POINTER(c_int), c_int, c_void_p, c_void_p],
     "avr_stream_copy": [c_void_p, c_void_p, i64, c_void_p],
     "avr_stream_fill": [c_void_p, i64, c_uint32, c_void_p],
 }

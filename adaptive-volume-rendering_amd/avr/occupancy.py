@@ -24,6 +24,20 @@ handful of view directions, so a density feature thinner than a cell, or one tha
 be missed: `dilate` (cells of safety margin around every occupied cell) and `sigma_thr` trade that risk against the
 live share. sigma_thr = 0.0 (the default) keeps every cell where any evaluated sigma is above exactly zero after the
 ReLU; a positive threshold also drops faint fog, which changes the image by up to the weight that fog carried.
+
+    grid = OccupancyGrid.from_field(net, lo, hi, res=(128, 128, 128), refine=4)      # hierarchical build
+
+builds a coarse grid densely first (res / refine, here 32^3: 1/64 of the cells) and evaluates fine cells only under
+its live cells (refine_from_field: children -> scan -> one host read of the candidate count M -> points -> field on
+the point list per MLP and direction -> flag_sigma -> build_sparse); every buffer is sized by M, no (K, cells) plane
+buffer is made. A fine cell under a clear coarse cell is never evaluated and counts as sigma = 0, so what the coarse
+stage calls empty is lost whatever the fine field holds there. The coarse stage judges a coarse cell at its centre
+alone -- one point per refine^3 fine cells -- so a feature narrower than a coarse cell that misses the centre of
+every coarse cell it crosses is dropped, where the dense build would have met it at a fine centre. `coarse_dilate`
+(default 1: a coarse cell stays live next to any live one, a margin of `refine` fine cells) and `coarse_probe` = p
+(the coarse stage evaluated at res * p / refine and OR-ed down by p: p^3 interior points per coarse cell at p^3
+times the coarse cost) trade that risk against the candidate share; neither is a guarantee.
+cells_missing_from(dense) counts what a hierarchical grid dropped relative to a dense one.
 """
 import ctypes
 
@@ -36,6 +50,8 @@ from .cache import _version_key
 
 F32 = torch.float32
 AXIS_DIRS = ((1.0, 0.0, 0.0), (-1.0, 0.0, 0.0), (0.0, 1.0, 0.0), (0.0, -1.0, 0.0), (0.0, 0.0, 1.0), (0.0, 0.0, -1.0))
+REFINE_FACTORS = (2, 4, 8)   # fine cells per coarse cell and axis of a hierarchical build (avr_occ_children)
+PROBE_FACTORS = (1, 2, 4)    # cells per coarse cell and axis of its dense probe (avr_occ_downsample)
 
 
 def _check_res(res):
@@ -80,7 +96,10 @@ class OccupancyGrid:
             raise ValueError(f"occupancy grid bits: {n_words(self.res)} int32 words for res {self.res}")
         self.bits = bits.reshape(-1).contiguous()
         self.key, self._keep = key, keep
-        self.inv = tuple(float(np.float32(r / (float(h) - float(l)))) for r, l, h in zip(self.res, self.lo, self.hi))
+        # from_field / refine_from_field: the candidates of a hierarchical build (None: built densely) and the field
+        # points evaluated for this grid (None: not built from a field)
+        self.n_candidates, self.build_evals = None, None
+        self.inv =tuple(float(np.float32(r / (float(h) - float(l)))) for r, l, h in zip(self.res, self.lo, self.hi))
         self.desc = OccGrid((ctypes.c_float * 3)(*self.lo), (ctypes.c_float * 3)(*self.inv),
                             (ctypes.c_int * 3)(*self.res), self.bits.data_ptr())
 
@@ -98,6 +117,7 @@ class OccupancyGrid:
                              f".. {self.hi} res {self.res}: the box and the resolution must match")
         self.bits.copy_(other.bits)
         self.key, self._keep = other.key, other._keep
+        self.n_candidates, self.build_evals = other.n_candidates, other.build_evals
         return self
 
     def live_fraction(self):
@@ -143,11 +163,19 @@ class OccupancyGrid:
         return torch.from_numpy(np.stack([xx, yy, zz], -1).reshape(-1, 3).astype(np.float32)).to(device)
 
     @classmethod
-    def from_field(cls, net, lo, hi, res=(128, 128, 128), sigma_thr=0.0, dilate=1, dirs=None, sb=0, chunk=1 << 20):
+    def from_field(cls, net, lo, hi, res=(128, 128, 128), sigma_thr=0.0, dilate=1, dirs=None, sb=0, chunk=1 << 20,
+                   refine=None, coarse_dilate=1, coarse_probe=1):
         """The grid of scene `sb` of a fusable NewPixelNeRFNet: sigma (output channel 3) of both MLPs, coarse and
         fine if present, at every cell centre for every view direction in `dirs` (default: the six axis directions
         -- the MLP sees the view direction, so one is not enough), `chunk` points per field launch, then from_sigma
-        over all those planes. The grid records the field_key() it was built under (stale())."""
+        over all those planes. The grid records the field_key() it was built under (stale()) and the field points it
+        evaluated (build_evals).
+        refine = f (2, 4 or 8; None, the default: the dense build above): the hierarchical build of the module
+        docstring -- a dense probe at res * coarse_probe / f with dilate = coarse_dilate, probe.downsample(
+        coarse_probe), then refine_from_field under that coarse grid; build_evals counts both stages."""
+        if refine is not None:
+            return cls._from_field_refined(net, lo, hi, res, sigma_thr, dilate, dirs, sb, chunk, refine,
+                                           coarse_dilate, coarse_probe)
         from .field import fused_eligible
         if not fused_eligible(net):
             raise ValueError("OccupancyGrid.from_field: the net is not on the single-view fused path")
@@ -170,7 +198,167 @@ class OccupancyGrid:
                         out = fused.forward_points_scene(p, vd.expand(p.shape[0], 3), coarse, sb)
                         planes[k, c0:c0 + p.shape[0]] = out[:, 3]
                     k += 1
-            return cls.from_sigma(planes.reshape(-1, res[2], res[1], res[0]), lo, hi, sigma_thr, dilate, key, keep)
+            grid = cls.from_sigma(planes.reshape(-1, res[2], res[1], res[0]), lo, hi, sigma_thr, dilate, key, keep)
+        grid.build_evals = planes.shape[0] * n
+        return grid
+
+    @classmethod
+    def _from_field_refined(cls, net, lo, hi, res, sigma_thr, dilate, dirs, sb, chunk, refine, coarse_dilate,
+                            coarse_probe):
+        res = _check_res(res)
+        f, p = int(refine), int(coarse_probe)
+        if f not in REFINE_FACTORS or p not in PROBE_FACTORS:
+            raise ValueError(f"OccupancyGrid.from_field: refine must be one of {REFINE_FACTORS} (got {refine!r}) and "
+                             f"coarse_probe one of {PROBE_FACTORS} (got {coarse_probe!r})")
+        if any(r % f for r in res) or (res[0] // f) % 32:
+            raise ValueError(f"OccupancyGrid.from_field: res {res} with refine {f}: every value must be divisible by "
+                             "it and the coarse res[0] a multiple of 32")
+        _check_thr("OccupancyGrid.from_field", sigma_thr)
+        probe = cls.from_field(net, lo, hi, tuple(r // f * p for r in res), sigma_thr, coarse_dilate, dirs, sb, chunk)
+        coarse = probe.downsample(p)
+        grid = cls.refine_from_field(net, coarse, f, sigma_thr, dilate, dirs, sb, chunk, lo=lo, hi=hi)
+        grid.build_evals += probe.build_evals
+        return grid
+
+    @classmethod
+    def refine_from_field(cls, net, coarse, factor, sigma_thr=0.0, dilate=1, dirs=None, sb=0, chunk=1 << 20, lo=None,
+                          hi=None):
+        """The fine grid of resolution coarse.res * factor (factor 2, 4 or 8) over coarse's box, with the field of
+        scene `sb` evaluated only at the centres of the fine cells under coarse's live cells (the candidates, M =
+        factor^3 * the live coarse cells, in linear fine-cell order): a fine cell is set iff a candidate within
+        `dilate` cells of it has not (sigma <= sigma_thr) for some MLP and direction -- from_field's bits with sigma
+        taken as 0 wherever coarse is clear. One host read (M) sizes every buffer; M == 0 launches no field. The
+        result carries n_candidates = M and build_evals = M * MLPs * directions, and records field_key(net).
+        ValueError: a net off the single-view fused path; a `coarse` that was built from a field and is stale for
+        `net` (a grid without a key, such as all_occupied, is accepted); a factor, a fine resolution or a box (lo /
+        hi, when given: compared with coarse's as float32) that does not fit; sigma_thr negative or NaN, which would
+        call the unevaluated cells occupied."""
+        from .field import fused_eligible
+        who = "OccupancyGrid.refine_from_field"
+        f = int(factor)
+        if f not in REFINE_FACTORS:
+            raise ValueError(f"{who}: factor must be one of {REFINE_FACTORS}, got {factor!r}")
+        if max(coarse.res) * f > _lib.OCC_MAX_RES:
+            raise ValueError(f"{who}: coarse res {coarse.res} times {f} exceeds {_lib.OCC_MAX_RES} cells per axis")
+        for name, given, own in (("lo", lo, coarse.lo), ("hi", hi, coarse.hi)):
+            if given is not None and tuple(float(np.float32(v)) for v in given) != own:
+                raise ValueError(f"{who}: box {name} {tuple(given)} is not the coarse grid's {own}")
+        if int(dilate) not in (0, 1, 2):
+            raise ValueError(f"{who}: dilate must be 0, 1 or 2")
+        thr = _check_thr(who, sigma_thr)
+        if not fused_eligible(net):
+            raise ValueError(f"{who}: the net is not on the single-view fused path")
+        if coarse.stale(net):
+            raise ValueError(f"{who}: the coarse grid was built from parameters, a latent map or source views that "
+                             "have changed since; rebuild it")
+        res = tuple(r * f for r in coarse.res)
+        dev = net.encoder.latent.device
+        fused = net.fused()
+        dirs = AXIS_DIRS if dirs is None else dirs
+        passes = [True] + ([False] if net.mlp_fine is not None else [])
+        key, keep = field_key(net)
+        chunk = int(chunk)
+        with torch.no_grad():
+            mask, counts = children(coarse, f, res)
+            offsets, total = scan(counts)
+            M = int(total.item())                        # the one host read: it sizes everything below
+            flags = None
+            if M:
+                xyz, vd = child_points(mask, offsets, res, coarse.lo, coarse.hi, M, dirs[0])
+                flags = torch.empty(M, dtype=torch.uint8, device=dev)
+                k = 0
+                for is_coarse in passes:
+                    for d in dirs:
+                        if k:
+                            child_points(mask, offsets, res, coarse.lo, coarse.hi, M, d, xyz=False, viewdirs=vd)
+                        for c0 in range(0, M, chunk):
+                            out = fused.forward_points_scene(xyz[c0:c0 + chunk], vd[c0:c0 + chunk], is_coarse, sb)
+                            flag_sigma(out, thr, k == 0, flags[c0:c0 + chunk])
+                        k += 1
+            bits = build_sparse(mask, offsets, flags, M, res, int(dilate))
+        grid = cls(coarse.lo, coarse.hi, res, bits, key, keep)
+        grid.n_candidates, grid.build_evals = M, M * len(passes) * len(dirs)
+        return grid
+
+    def downsample(self, p):
+        """The grid of resolution res / p (p 1, 2 or 4; every res[a] divisible by it, res[0] / p a multiple of 32)
+        over the same box whose cell is set iff any of its p^3 children is (avr_occ_downsample). It keeps this grid's
+        key."""
+        p = int(p)
+        if p not in PROBE_FACTORS or any(r % p for r in self.res) or (self.res[0] // p) % 32:
+            raise ValueError(f"OccupancyGrid.downsample: p = {p} with res {self.res}: p must be one of "
+                             f"{PROBE_FACTORS}, divide every value and leave res[0] / p a multiple of 32")
+        require_device(self.bits)
+        res = tuple(r // p for r in self.res)
+        bits = torch.empty(n_words(res), dtype=torch.int32, device=self.device)
+        call("avr_occ_downsample", ptr(self.bits), (ctypes.c_int * 3)(*self.res), p, ptr(bits), stream_of(bits))
+        grid = type(self)(self.lo, self.hi, res, bits, self.key, self._keep)
+        grid.build_evals = self.build_evals
+        return grid
+
+    def cells_missing_from(self, other):
+        """How many cells `other` (same box and resolution, else ValueError) sets that this grid leaves clear: what
+        a hierarchical grid dropped relative to a dense one. A host read of both grids' bits."""
+        if other.res != self.res or other.lo != self.lo or other.hi != self.hi:
+            raise ValueError(f"OccupancyGrid.cells_missing_from: box {other.lo} .. {other.hi} res {other.res} against "
+                             f"box {self.lo} .. {self.hi} res {self.res}: the box and the resolution must match")
+        mine, theirs = (g.bits.cpu().numpy().view(np.uint8) for g in (self, other))
+        return int(np.unpackbits(theirs & ~mine).sum())
+
+
+def _check_thr(who, sigma_thr):
+    thr = float(sigma_thr)
+    if not thr >= 0.0:
+        raise ValueError(f"{who}: sigma_thr {sigma_thr!r} must be >= 0 for a hierarchical build (a negative or NaN "
+                         "threshold would call the cells that are never evaluated occupied)")
+    return thr
+
+
+def children(coarse, factor, res):
+    """avr_occ_children: the fine cells of `res` under coarse's live cells -> mask (ry * rz, ceil(rx / 64)) int64
+    (the uint64 words' bits), counts (ry * rz,) int32."""
+    require_device(coarse.bits)
+    rows = res[1] * res[2]
+    mask = torch.empty(rows, (res[0] + 63) // 64, device=coarse.device, dtype=torch.int64)
+    counts = torch.empty(rows, device=coarse.device, dtype=torch.int32)
+    call("avr_occ_children", ctypes.byref(coarse.desc), int(factor), (ctypes.c_int * 3)(*res), ptr(mask), ptr(counts),
+         stream_of(mask))
+    return mask, counts
+
+
+def refine_axes(lo, hi, res):
+    """lo64[a] = double(float32 lo[a]) and step[a] = (hi64[a] - lo64[a]) / res[a], in double: cell_centres' terms."""
+    lo64 = [float(np.float32(v)) for v in lo]
+    return lo64, [(float(np.float32(h)) - l) / r for l, h, r in zip(lo64, hi, res)]
+
+
+def child_points(mask, offsets, res, lo, hi, n_live, direction, xyz=None, viewdirs=None):
+    """avr_occ_child_points -> xyz, viewdirs (n_live, 3): the candidates' centres (the rows of cell_centres at the
+    candidates, bit for bit) and `direction` in every row. xyz / viewdirs: a tensor to write into, None to allocate
+    one, False to leave that output out (not both)."""
+    make = lambda t: torch.empty(n_live, 3, device=mask.device, dtype=F32) if t is None else t  # noqa: E731
+    xyz, viewdirs = (None if t is False else make(t) for t in (xyz, viewdirs))
+    lo64, step = refine_axes(lo, hi, res)
+    call("avr_occ_child_points", ptr(mask), ptr(offsets), (ctypes.c_int * 3)(*res), (ctypes.c_double * 3)(*lo64),
+         (ctypes.c_double * 3)(*step), (ctypes.c_float * 3)(*[float(v) for v in direction]), n_live, ptr(xyz),
+         ptr(viewdirs), stream_of(mask))
+    return xyz, viewdirs
+
+
+def flag_sigma(field_c, thr, first, flags):
+    """avr_occ_flag_sigma: flags[q] = (0 if first else flags[q]) | not (field_c[q, 3] <= thr), in place (uint8)."""
+    require_device(field_c, flags)
+    call("avr_occ_flag_sigma", ptr(field_c), float(thr), int(bool(first)), field_c.shape[0], ptr(flags),
+         stream_of(field_c))
+    return flags
+
+
+def build_sparse(mask, offsets, flags, n_live, res, dilate):
+    """avr_occ_build_sparse -> bits (n_words(res),) int32; flags may be None with n_live == 0."""
+    bits = torch.empty(n_words(res), dtype=torch.int32, device=mask.device)
+    call("avr_occ_build_sparse", ptr(mask), ptr(offsets), ptr(flags), n_live, (ctypes.c_int * 3)(*res), int(dilate),
+         ptr(bits), stream_of(bits))
+    return bits
 
 
 def classify(grid, ro, rd, z):

@@ -5,6 +5,7 @@ harness, utils.py:481-537, on the fused path; BASELINE configs 4 and 5).
     torchrun --nproc-per-node N -m avr.render ...   # rays of every frame sharded over N GPUs
     python -m avr.render --renderer adaptive --n-coarse 20 --philox-seed 3   # in-kernel draws: reproducible frames
     python -m avr.render --occupancy 128 [--occupancy-sigma 0.0]   # skip empty space (avr.occupancy); prints the live share
+    python -m avr.render --occupancy 128 --occupancy-refine 4      # the grid built hierarchically: the field only under a live 32^3 grid
     python -m avr.render --occupancy 128 --occupancy-count device  # the same with the live count kept on the device
     python -m avr.render --t-stop 1e-3 --t-stop-count device [--occupancy 128]   # termination without host reads
 
@@ -84,6 +85,13 @@ def main(argv=None):
                          "(default 0.0: exactly zero after the ReLU), before one cell of dilation")
     ap.add_argument("--occupancy-box", type=float, default=1.0, metavar="HALF",
                     help="the grid covers [-HALF, HALF]^3; samples outside it count as empty")
+    ap.add_argument("--occupancy-refine", type=int, default=None, metavar="F",
+                    help="with --occupancy: build the grid hierarchically (F = 2, 4 or 8): a (RES / F)^3 grid is built "
+                         "densely and the field evaluated only at the fine cells under its live cells; what that "
+                         "coarse grid calls empty is never looked at again")
+    ap.add_argument("--occupancy-probe", type=int, default=None, metavar="P",
+                    help="with --occupancy-refine: judge every coarse cell at P^3 interior points (P = 1, 2 or 4; "
+                         "default 1: its centre alone) at P^3 times the coarse stage's cost")
     ap.add_argument("--occupancy-count", choices=("host", "device"), default=None,
                     help="with --occupancy: where the live count of a gated pass is kept. host (default): read back "
                          "once per pass to size the launches; device: never read back, worst-case buffers (40 B per "
@@ -96,9 +104,12 @@ def main(argv=None):
     ap.add_argument("--out", default=None, help="directory for frame_XXX.ppm")
     args = ap.parse_args(argv)
     from .renderers import check_skip_modes
+    from .video import check_refine_modes
     try:   # the counts as given (None: flag not given), so that a count given without its feature is refused too
+        flag = lambda n: "--" + n.replace("_", "-")  # noqa: E731
         check_skip_modes("", args.t_stop, args.t_stop_count, args.occupancy, args.occupancy_count, idle=None,
-                         name=lambda n: "--" + n.replace("_", "-"))
+                         name=flag)
+        check_refine_modes("", args.occupancy, args.occupancy_refine, args.occupancy_probe, idle=None, name=flag)
     except ValueError as e:
         ap.error(str(e))
     t_stop_count, occupancy_count = args.t_stop_count or "host", args.occupancy_count or "host"
@@ -142,8 +153,13 @@ def main(argv=None):
         if args.occupancy is not None:   # once per scene, before the frames (after the broadcast: every rank's own)
             from .occupancy import OccupancyGrid
             h = args.occupancy_box
+            torch.cuda.synchronize()
+            t_build = time.perf_counter()
             rend.occupancy = OccupancyGrid.from_field(net, (-h, -h, -h), (h, h, h), (args.occupancy,) * 3,
-                                                      sigma_thr=args.occupancy_sigma)
+                                                      sigma_thr=args.occupancy_sigma, refine=args.occupancy_refine,
+                                                      coarse_probe=args.occupancy_probe or 1)
+            torch.cuda.synchronize()
+            occupancy_build_ms = (time.perf_counter() - t_build) * 1e3
             rend.occupancy_count = occupancy_count
     K = torch.tensor([INTRINSICS], device=device)
     H = W = args.res
@@ -200,7 +216,9 @@ def main(argv=None):
         if args.occupancy is not None:
             # the live share: field samples evaluated over both passes' n_coarse + (n_coarse + n_fine) per ray
             line.update({"occupancy": args.occupancy, "occupancy_sigma": args.occupancy_sigma,
-                         "occupancy_count": occupancy_count,
+                         "occupancy_count": occupancy_count, "occupancy_refine": args.occupancy_refine,
+                         "occupancy_build_evals": rend.occupancy.build_evals,
+                         "occupancy_build_ms": round(occupancy_build_ms, 3),
                          "occupancy_cells_set": round(rend.occupancy.live_fraction(), 4),
                          "live_samples_fraction": round(live_samples / (args.frames * n * (2 * args.n_coarse
                                                                                           + args.n_fine)), 4)})

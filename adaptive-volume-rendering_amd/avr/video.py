@@ -94,9 +94,30 @@ class FrameCounts:
         return tuple(int(s.sum().item()) if torch.is_tensor(s) else s for s in self._sums)
 
 
+def check_refine_modes(who, occupancy, refine, probe, idle=None, name=str):
+    """The hierarchical grid build's two arguments, in check_skip_modes' style: refine (2, 4 or 8) and probe (1, 2 or
+    4) need occupancy = RES, RES must be divisible by refine with RES / refine a multiple of 32, and probe needs
+    refine; ValueError otherwise. `idle`: what probe holds when it was not given (render_orbit: 1, its default; the
+    CLI: None). `name` spells the names in the caller's vocabulary."""
+    from .occupancy import PROBE_FACTORS, REFINE_FACTORS
+    if refine is None:
+        if probe != idle:
+            raise ValueError(f"{who}{name('occupancy_probe')} needs {name('occupancy_refine')}")
+        return
+    if occupancy is None:
+        raise ValueError(f"{who}{name('occupancy_refine')} needs {name('occupancy')}")
+    if refine not in REFINE_FACTORS:
+        raise ValueError(f"{who}{name('occupancy_refine')} must be one of {REFINE_FACTORS}, got {refine!r}")
+    if probe not in PROBE_FACTORS + (idle,):
+        raise ValueError(f"{who}{name('occupancy_probe')} must be one of {PROBE_FACTORS}, got {probe!r}")
+    if int(occupancy) % refine or (int(occupancy) // refine) % 32:
+        raise ValueError(f"{who}{name('occupancy_refine')} {refine} needs {name('occupancy')} = a multiple of "
+                         f"{32 * refine}, got {occupancy}")
+
+
 def render_orbit(renderer, radiance_field, intrinsics, num_frames, radius, height, width=None, fine=True,
                  device=None, t_stop=None, on_frame=None, occupancy=None, occupancy_sigma=0.0, occupancy_box=1.0,
-                 occupancy_count="host", t_stop_count="host"):
+                 occupancy_count="host", t_stop_count="host", occupancy_refine=None, occupancy_probe=1):
     """Render num_frames full frames around the orbit with `renderer`
     (e.g. avr.renderers.VolumeRenderer) and a ready radiance field. One
     renderer call per frame (all H * W rays at once), no_grad. Returns
@@ -110,9 +131,13 @@ def render_orbit(renderer, radiance_field, intrinsics, num_frames, radius, heigh
     its live count back; the counts are summed on the device and read once after the last frame.
     t_stop_count = "host" | "device" (renderer.t_stop_count for these frames; "device" needs t_stop): with "device"
     the fine pass is terminated, and with occupancy also gated, without a host read; the evaluated fine samples are
-    summed on the device and read once after the last frame."""
+    summed on the device and read once after the last frame.
+    occupancy_refine = F (2, 4 or 8), occupancy_probe = P (1, 2 or 4): the grid is built hierarchically
+    (from_field(refine=F, coarse_probe=P): the field only under the live cells of a (RES / F)^3 grid); both need
+    occupancy. stats then carry occupancy_build_evals and occupancy_build_ms."""
     from .renderers import check_skip_modes
     check_skip_modes("render_orbit: ", t_stop, t_stop_count, occupancy, occupancy_count, idle="host")
+    check_refine_modes("render_orbit: ", occupancy, occupancy_refine, occupancy_probe, idle=1)
     width = width or height
     device = device or intrinsics.device
     K = intrinsics.reshape(1, 3, 3).to(device)
@@ -122,8 +147,16 @@ def render_orbit(renderer, radiance_field, intrinsics, num_frames, radius, heigh
     if occupancy is not None:
         from .occupancy import OccupancyGrid
         h = float(occupancy_box)
+        on_gpu = torch.device(device).type == "cuda"      # (elsewhere from_field raises before any launch)
+        if on_gpu:
+            torch.cuda.synchronize(device)
+        t_build = time.perf_counter()
         grid = OccupancyGrid.from_field(radiance_field, (-h, -h, -h), (h, h, h), (int(occupancy),) * 3,
-                                        sigma_thr=occupancy_sigma)
+                                        sigma_thr=occupancy_sigma, refine=occupancy_refine,
+                                        coarse_probe=occupancy_probe)
+        if on_gpu:
+            torch.cuda.synchronize(device)
+        build_ms = (time.perf_counter() - t_build) * 1e3
     modes = {"t_stop": t_stop}
     if t_stop is not None:
         modes["t_stop_count"] = t_stop_count
@@ -154,19 +187,22 @@ def render_orbit(renderer, radiance_field, intrinsics, num_frames, radius, heigh
         per_ray = 2 * renderer.n_coarse + renderer.n_fine    # the coarse pass, then coarse + fine positions again
         stats["live_share"] = live_samples / max(num_frames * n * per_ray, 1)
         stats["occupancy_count"] = occupancy_count
+        stats.update(occupancy_refine=occupancy_refine, occupancy_build_evals=grid.build_evals,
+                     occupancy_build_ms=build_ms)
         print(f"occupancy {occupancy}^3: {stats['live_share']:.4f} of the field samples were live")
     return frames, stats
 
 
 def generate_video(model_input, num_frames, radius, net, model, fine=True, occupancy=None, occupancy_count="host",
-                   t_stop_count="host"):
+                   t_stop_count="host", occupancy_refine=None, occupancy_probe=1):
     """utils.py:481-537 with the same arguments: encode the first source view
     of model_input into `net`, then render the orbit through `model`
     (a RadFieldAndRenderer). A net whose latent was set with encode_latent()
     keeps it (no `images` needed); otherwise the source view is encoded.
     occupancy = RES, occupancy_count = "host" | "device": render_orbit's empty-space skipping (not in the
     reference; off by default). t_stop_count = "host" | "device": where render_orbit keeps the counts of the
-    renderer's early termination (model.renderer.t_stop; "device" needs it set)."""
+    renderer's early termination (model.renderer.t_stop; "device" needs it set). occupancy_refine = F,
+    occupancy_probe = P: render_orbit's hierarchical grid build."""
     intrinsics = model_input["intrinsics"][0:1, 0, ...]
     if "images" in model_input and net.encoder.latent.shape[-1] <= 1:   # no latent yet
         gt = model_input["images"]
@@ -179,7 +215,8 @@ def generate_video(model_input, num_frames, radius, net, model, fine=True, occup
     t_stop = getattr(model.renderer, "t_stop", None) if t_stop_count == "device" else None
     frames, stats = render_orbit(model.renderer, net, intrinsics, num_frames, radius, sl, fine=fine,
                                  t_stop=t_stop, occupancy=occupancy,
-                                 occupancy_count=occupancy_count, t_stop_count=t_stop_count)
+                                 occupancy_count=occupancy_count, t_stop_count=t_stop_count,
+                                 occupancy_refine=occupancy_refine, occupancy_probe=occupancy_probe)
     print(f"it takes {stats['seconds']} seconds to render a video")
     return frames
 

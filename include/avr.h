@@ -763,6 +763,48 @@ int avr_field_fwd_points_counted(const avr_field_dims* dims, const avr_view_desc
                                  const float* table, const float* xyz, const float* viewdirs, int64_t capacity,
                                  const int64_t* n_points, float* out, void* stream);
 
+/* ------------------------------------ occupancy grid: hierarchical build
+ * Additions within ABI 18 (no version change; DESIGN.md "Occupancy grid: hierarchical build"): the field is evaluated
+ * at the fine cells under live coarse cells only, by the gating chain with a fine x-row for the ray and a cell of the
+ * row for the sample:
+ *   avr_occ_children -> avr_occ_scan -> (one host read of the total) -> avr_occ_child_points
+ *     -> per plane: the field on the point list, avr_occ_flag_sigma -> avr_occ_build_sparse
+ * Shapes: the fine grid has res = (rx, ry, rz) within the limits above; factor f in {2, 4, 8}; every res[a] % f == 0;
+ * the coarse grid C has res rc = res / f, rc[0] % 32 == 0, over the same box.
+ * Candidates: fine cell (ix, iy, iz) is a candidate iff bit (ix / f, iy / f, iz / f) of C is set. They are ordered by
+ * the linear fine index (iz * ry + iy) * rx + ix, ascending; the order does not depend on the data. mask is
+ * (ry * rz, ceil(rx / 64)) uint64: row iz * ry + iy, bit ix % 64 of word ix / 64 (bits at or past rx clear); counts
+ * int32 per row; offsets and total are avr_occ_scan's over the ry * rz rows; M = total = f^3 * popcount(C). A
+ * candidate's rank is offsets[row] + popcount of the lower mask bits of its row. No atomics, no slot array, no
+ * memset: every output is bit-reproducible.
+ *   avr_occ_children: coarse descriptor (its box is not read), f, fine res -> mask, counts; every element written.
+ *   avr_occ_child_points: xyz[rank] = (c_x, c_y, c_z), c_a = (float)(lo64[a] + (i_a + 0.5) * step[a]) with lo64[a] =
+ *     (double)(float)lo[a] and step[a] = (hi64[a] - lo64[a]) / res[a] computed once by the caller in double (host
+ *     arrays of three); the product and the sum are each rounded once in double, never fused. viewdirs[rank] = dir
+ *     (host array of three floats). xyz or viewdirs may be NULL (not both): one xyz serves several directions.
+ *   avr_occ_flag_sigma: field_c (n_live, 4; 16-B aligned), sigma = channel 3 -> flags (n_live) bytes:
+ *     flags[q] = (first ? 0 : flags[q]) | !(sigma[q] <= thr); NaN counts as occupied. thr must be >= 0.
+ *   avr_occ_build_sparse: fine cell c is set iff some cell within Chebyshev distance dilate (0, 1 or 2, clamped at
+ *     the faces) of c is a candidate whose flag is set; every word of bits is written; n_live == 0 writes zeros and
+ *     reads neither mask, offsets nor flags (they may be NULL). These are the bits avr_occ_build gives for planes
+ *     that hold the evaluated sigma at the candidates and 0 elsewhere, which is why thr < 0 (and NaN) is refused: it
+ *     would call unevaluated cells occupied.
+ *   avr_occ_downsample: p in {1, 2, 4}, res[a] % p == 0, (res[0] / p) % 32 == 0 -> coarse_bits of res / p: the OR of
+ *     the p^3 children; every word written.
+ * Checked before any launch (AVR_E_INVALID): null pointers, res out of range, factor, p, divisibility, a coarse res
+ * that is not res / factor, dilate outside 0 .. 2, thr negative or NaN, n_live outside 0 .. rx * ry * rz, mask or
+ * offsets not 8-B aligned, field rows not 16-B aligned. avr_occ_child_points and avr_occ_flag_sigma with n_live == 0
+ * return AVR_OK with no launch.                                                                                    */
+int avr_occ_children(const avr_occ_grid* coarse, int factor, const int* res, uint64_t* mask, int32_t* counts,
+                     void* stream);
+int avr_occ_child_points(const uint64_t* mask, const int64_t* offsets, const int* res, const double* lo64,
+                         const double* step, const float* dir, int64_t n_live, float* xyz, float* viewdirs,
+                         void* stream);
+int avr_occ_flag_sigma(const float* field_c, float thr, int first, int64_t n_live, uint8_t* flags, void* stream);
+int avr_occ_build_sparse(const uint64_t* mask, const int64_t* offsets, const uint8_t* flags, int64_t n_live,
+                         const int* res, int dilate, uint32_t* bits, void* stream);
+int avr_occ_downsample(const uint32_t* bits, const int* res, int p, uint32_t* coarse_bits, void* stream);
+
 /* ------------------------------- fine pass, early termination on the device
  * Additions within ABI 18 (no version change; DESIGN.md "Early termination: device-side chain"): the early
  * termination of avr_march_* with every count kept on the device, combinable with an occupancy grid. No host read
