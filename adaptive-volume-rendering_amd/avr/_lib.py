@@ -51,6 +51,7 @@ class FieldDims(ctypes.Structure):
 
 FIELD_FP32 = 0
 FIELD_X3 = 1
+FIELD_FP16 = 2   # single-product fp16 MFMA on the x3 blob (inference only; include/avr.h AVR_FIELD_FP16)
 
 
 class ResnetFCWeights(ctypes.Structure):

@@ -54,7 +54,7 @@ def bn_train_eligible(net):
         try:
             for mod, _ in saved:
                 mod.training = False
-            return fused_eligible(net)
+            return fused_eligible(net, train=True)
         finally:
             for mod, t in saved:
                 mod.training = t

@@ -80,18 +80,22 @@ def _resnetfc_ok(mlp, d_in, d_latent, precision="x3"):
     return all(not blk.bn or _bn_ok(blk) for blk in mlp.blocks)
 
 
-def fused_eligible(net, multiview=False):
+def fused_eligible(net, multiview=False, train=False):
     """True when `net` is a NewPixelNeRFNet configured like conf/default*.conf:
     local encoder, xyz + PE(xyz) + raw viewdirs, normalize_z, bilinear/border
     latent lookup, ResNet MLPs (eval-mode BatchNorm, use_spade and Softplus
     allowed on the x3 path), one source view. multiview: instead NS > 1 source
     views, x3, every MLP combining them (combine_layer < n_blocks, mean or max):
-    FusedField.forward_points_multiview."""
+    FusedField.forward_points_multiview. train: for a call that needs gradients, where "fp16" (inference only)
+    means what "x3" means."""
     try:
         ns = net.num_views_per_obj
+        precision = getattr(net, "field_precision", "x3")
+        if train:
+            precision = blob_precision(precision)
         if multiview:
             mlps = [net.mlp_coarse] + ([net.mlp_fine] if net.mlp_fine is not None else [])
-            if not (ns > 1 and getattr(net, "field_precision", "x3") == "x3"
+            if not (ns > 1 and precision == "x3"
                     and all(1 <= m.combine_layer < m.n_blocks and m.combine_type in ("average", "max")
                             for m in mlps)):
                 # combine_layer 0 (views combined right after lin_in, no lin_z): module path -- the split
@@ -111,7 +115,6 @@ def fused_eligible(net, multiview=False):
         if not ok:
             return False
         mlps = [net.mlp_coarse] + ([net.mlp_fine] if net.mlp_fine is not None else [])
-        precision = getattr(net, "field_precision", "x3")
         return all(_resnetfc_ok(m, net.d_in, net.d_latent, precision) for m in mlps)
     except AttributeError:
         return False
@@ -124,7 +127,13 @@ def _freq_factor(code):
     return float(ff)
 
 
-PRECISIONS = {"fp32": _lib.FIELD_FP32, "x3": _lib.FIELD_X3}
+PRECISIONS = {"fp32": _lib.FIELD_FP32, "x3": _lib.FIELD_X3, "fp16": _lib.FIELD_FP16}
+
+
+def blob_precision(precision):
+    """The precision a blob is packed and cached under: "fp16" reads the x3 blob byte for byte (its hi halves),
+    so the two share one _Packed record and one set of lin_z tables; "fp32" has its own."""
+    return "x3" if precision == "fp16" else precision
 
 
 class _Packed:
@@ -143,7 +152,7 @@ class _Packed:
         self._dims_as = {precision: dims.with_precision(precision) for precision in PRECISIONS.values()}
 
     def dims_as(self, precision):
-        """A copy of dims selecting the `precision` kernels (_lib.FIELD_X3 / _lib.FIELD_FP32): what a library
+        """A copy of dims selecting the `precision` kernels (_lib.FIELD_X3 / FIELD_FP32 / FIELD_FP16): what a library
         call is given, so that dims itself keeps describing the blob."""
         return self._dims_as[precision]
 
@@ -155,7 +164,9 @@ def n_tables(dims):
 
 class FusedField:
     """precision: "x3" (default) = split-fp16 MFMA (3 products per fp32 product,
-    fp32 accumulation, within fp32 noise of the fp32 path); "fp32" = fp32 MFMA."""
+    fp32 accumulation, within fp32 noise of the fp32 path); "fp32" = fp32 MFMA;
+    "fp16" = one fp16 product per term on the x3 blob (inference only, ~1e-4 mean rgb
+    error: for 8-bit frames; ReLU nets, one source view; training calls run x3)."""
 
     def __init__(self, net, precision="x3"):
         if precision not in PRECISIONS:
@@ -248,7 +259,8 @@ class FusedField:
         code = self.net.code
         return FieldDims(self.net.d_in, self.net.d_latent, mlp.d_hidden, mlp.n_blocks,
                          min(mlp.combine_layer, mlp.n_blocks), code.num_freqs, _freq_factor(code),
-                         PRECISIONS[self.precision], int(uses_bn(mlp)), int(getattr(mlp, "use_spade", False)),
+                         PRECISIONS[blob_precision(self.precision)], int(uses_bn(mlp)),
+                         int(getattr(mlp, "use_spade", False)),
                          float(softplus_beta(mlp) or 0.0))
 
     def packed(self, coarse, bn_fold=True):
@@ -260,7 +272,7 @@ class FusedField:
         # the precision is part of the key: an x3 blob holds only the fragments the x3 kernels read
         # (avr_field_pack), and net.fused() switches a FusedField's precision in place
         slot = coarse if bn_fold else (coarse, "bn_train")
-        key = (id(mlp), self.precision if bn_fold else "x3", _version_key(params))
+        key = (id(mlp), blob_precision(self.precision) if bn_fold else "x3", _version_key(params))
 
         def make():
             dims = self.dims(mlp)
@@ -429,13 +441,13 @@ class FusedField:
         z = z.to(F32).reshape(SB * R, N).contiguous()
         require_device(ro, rd, z)
         out = torch.empty(SB * R * N, 4, device=z.device, dtype=F32)
-        if self.precision != "x3":     # the fp32 kernel is single-scene
+        if self.precision == "fp32":     # the fp32 kernel is single-scene
             for b in range(SB):
                 out[b * R * N:(b + 1) * R * N] = self.forward_rays(ro[b], rd[b], z[b * R:(b + 1) * R], coarse, sb=b)
             return out
         entry = self.packed(coarse)
         tables = self.tables_batch(coarse, SB)
-        dims = entry.dims_as(_lib.FIELD_X3)
+        dims = entry.dims_as(PRECISIONS[self.precision])
         for g0, n in scene_groups(SB):
             views = self.views(range(g0, g0 + n))
             call("avr_field_fwd_rays_batch", ctypes.byref(dims), views, n, ptr(entry.packed), ptr(tables[g0]),
@@ -487,12 +499,12 @@ class FusedField:
         SB, B, _ = xyz.shape
         out = torch.empty(SB, B, 4, device=xyz.device, dtype=F32)
         entry = self.packed(coarse)
-        if SB > 1 and self.precision == "x3":   # one launch per group of scenes
+        if SB > 1 and self.precision != "fp32":   # one launch per group of scenes
             p = xyz.to(F32).contiguous()
             v = viewdirs.reshape(SB, B, 3).to(F32).contiguous()
             require_device(p, v)
             tables = self.tables_batch(coarse, SB)
-            dims = entry.dims_as(_lib.FIELD_X3)
+            dims = entry.dims_as(PRECISIONS[self.precision])
             for g0, n in scene_groups(SB):
                 views = self.views(range(g0, g0 + n))
                 call("avr_field_fwd_points_batch", ctypes.byref(dims), views, n, ptr(entry.packed),

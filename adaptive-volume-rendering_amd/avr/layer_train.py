@@ -43,9 +43,9 @@ def layer_train_eligible(net):
             return False
         if not (ns > 1 or any(getattr(m, "use_spade", False) for m in mlps)):
             return False
-        if not (net.d_latent % 64 == 0 and net.d_latent <= 512 and getattr(net, "field_precision", "x3") == "x3"):
+        if not (net.d_latent % 64 == 0 and net.d_latent <= 512 and getattr(net, "field_precision", "x3") in ("x3", "fp16")):
             return False
-        return fused_eligible(net, multiview=ns > 1)
+        return fused_eligible(net, multiview=ns > 1, train=True)
     except AttributeError:
         return False
 

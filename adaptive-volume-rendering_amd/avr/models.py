@@ -193,7 +193,7 @@ class NewPixelNeRFNet(nn.Module):
         self.d_in, self.d_out, self.d_latent = d_in, 4, d_latent
         self.num_objs, self.num_views_per_obj = 0, 1
         self.use_fused = True           # HIP field under no_grad (avr.field)
-        self.field_precision = "x3"     # "x3" split-fp16 MFMA | "fp32" MFMA
+        self.field_precision = "x3"     # "x3" split-fp16 MFMA | "fp32" MFMA | "fp16" one product (inference only)
         self.hip_backward = True        # autograd through the HIP field (avr.field._FieldTrain)
         self._fused = None
 
@@ -274,7 +274,7 @@ class NewPixelNeRFNet(nn.Module):
         adaptive renderer's band points); view directions must not."""
         from .field import fused_eligible, inference_only
         return (self.use_fused and self.hip_backward and xyz.is_cuda and torch.is_grad_enabled()
-                and viewdirs is not None and not viewdirs.requires_grad and fused_eligible(self)
+                and viewdirs is not None and not viewdirs.requires_grad and fused_eligible(self, train=True)
                 and not any(inference_only(m) for m in (self.mlp_coarse, self.mlp_fine) if m is not None))
 
     def can_fuse_multiview(self, xyz):

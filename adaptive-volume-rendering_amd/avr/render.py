@@ -64,7 +64,7 @@ def main(argv=None):
     ap.add_argument("--near", type=float, default=0.8)
     ap.add_argument("--far", type=float, default=1.8)
     ap.add_argument("--t-stop", type=float, default=None, help="early ray termination of the fine pass")
-    ap.add_argument("--precision", choices=["x3", "fp32"], default="x3")
+    ap.add_argument("--precision", choices=["x3", "fp32", "fp16"], default="x3")
     ap.add_argument("--sigma-bias", type=float, default=0.0, help="synthetic scene: density bias (opacity)")
     ap.add_argument("--weights", default=None, help="NewPixelNeRFNet state_dict (torch.save)")
     ap.add_argument("--latent", default=None, help=".npy latent map (1, 512, H, W)")

@@ -323,9 +323,22 @@ static int field_common(const avr_field_dims* dims, const avr_view_desc* view, c
   return AVR_OK;
 }
 
+// AVR_FIELD_FP16 reads the x3 fragments' hi halves: a blob packed for AVR_FIELD_X3 or AVR_FIELD_FP16 (the two
+// pack the same bytes and are recorded alike), never an fp32 one of another layout.
+static int fp16_blob_ok(const FieldArgs& a) {
+  AVR_REQUIRE(packed_precision(a.packed) != AVR_FIELD_FP32,
+              "field: the blob was packed for AVR_FIELD_FP32: pack it with AVR_FIELD_X3 or AVR_FIELD_FP16 to run "
+              "the fp16 kernel");
+  return AVR_OK;
+}
+
 static int dispatch_field(const avr_field_dims* dims, const FieldArgs& a, hipStream_t s) {
   const int d_hidden = dims->d_hidden;
   if (dims->precision == AVR_FIELD_X3) return dispatch_field_x3(d_hidden, a, s);
+  if (dims->precision == AVR_FIELD_FP16) {
+    if (int rc = fp16_blob_ok(a)) return rc;
+    return dispatch_field_fp16(d_hidden, a, s);
+  }
   AVR_REQUIRE(packed_precision(a.packed) != AVR_FIELD_X3,
               "field: the blob was packed for AVR_FIELD_X3 (no fp32 lin_in / fc_0 / fc_1 fragments): pack it with "
               "AVR_FIELD_FP32 to run the fp32 kernel");
@@ -342,6 +355,10 @@ static int dispatch_field_counted(const avr_field_dims* dims, const FieldArgs& a
     return fail(AVR_E_UNSUPPORTED, "avr_field_fwd_points_counted: BatchNorm, use_spade and Softplus nets have no "
                                    "counted kernel");
   if (dims->precision == AVR_FIELD_X3) return dispatch_field_x3_counted(dims->d_hidden, a, s);
+  if (dims->precision == AVR_FIELD_FP16) {
+    if (int rc = fp16_blob_ok(a)) return rc;
+    return dispatch_field_fp16(dims->d_hidden, a, s);
+  }
   AVR_REQUIRE(packed_precision(a.packed) != AVR_FIELD_X3,
               "field: the blob was packed for AVR_FIELD_X3 (no fp32 lin_in / fc_0 / fc_1 fragments): pack it with "
               "AVR_FIELD_FP32 to run the fp32 kernel");
@@ -363,10 +380,12 @@ extern "C" void avr_debug_set_flags(int f) { g_debug = f; }
 // Several scenes in one launch (x3 path): scene s's samples are rows s * per_scene .. of the inputs, its lin_z
 // tables at tables + s * max(n_tables, 1) * H*W * d_hidden (FusedField.tables_batch), its view views[s].
 static int field_batch(const avr_field_dims* dims, const avr_view_desc* views, int n_scenes, const float* packed,
-                       const float* tables, FieldArgs* a, int64_t per_scene, const char* what) {
+                       const float* tables, FieldArgs* a, int64_t per_scene, const char* what,
+                       bool fp16_too = false) {
   AVR_REQUIRE(views && n_scenes >= 1 && n_scenes <= AVR_MAX_SCENES, "%s: 1..%d scenes per call", what,
               AVR_MAX_SCENES);
-  AVR_REQUIRE(dims && dims->precision == AVR_FIELD_X3, "%s: the multi-scene launch is x3 only", what);
+  AVR_REQUIRE(dims && (dims->precision == AVR_FIELD_X3 || (fp16_too && dims->precision == AVR_FIELD_FP16)),
+              "%s: the multi-scene launch is %s", what, fp16_too ? "x3 or fp16" : "x3 only");
   int rc = field_common(dims, views, packed, tables, a);
   if (rc) return rc;
   for (int s = 0; s < n_scenes; ++s) {
@@ -504,13 +523,14 @@ extern "C" int avr_field_fwd_rays_batch(const avr_field_dims* dims, const avr_vi
                                         const float* z, int64_t n_rays, int n_samples, float* out, void* stream) {
   FieldArgs a{};
   AVR_REQUIRE(n_rays >= 0 && n_samples > 0, "avr_field_fwd_rays_batch: bad sizes");
-  int rc = field_batch(dims, views, n_scenes, packed, tables, &a, n_rays * n_samples, "avr_field_fwd_rays_batch");
+  int rc = field_batch(dims, views, n_scenes, packed, tables, &a, n_rays * n_samples, "avr_field_fwd_rays_batch",
+                       true);
   if (rc) return rc;
   AVR_REQUIRE(n_rays == 0 || (ro && rd && z && out), "avr_field_fwd_rays_batch: null pointer");
   a.ro = ro; a.rd = rd; a.z = z; a.n_samples = n_samples;
   a.out = reinterpret_cast<float4*>(out);
   if (a.M == 0) return AVR_OK;
-  return dispatch_field_x3(dims->d_hidden, a, as_stream(stream));
+  return dispatch_field(dims, a, as_stream(stream));
 }
 
 extern "C" int avr_field_fwd_points_batch(const avr_field_dims* dims, const avr_view_desc* views, int n_scenes,
@@ -518,13 +538,13 @@ extern "C" int avr_field_fwd_points_batch(const avr_field_dims* dims, const avr_
                                           const float* viewdirs, int64_t n_points, float* out, void* stream) {
   FieldArgs a{};
   AVR_REQUIRE(n_points >= 0, "avr_field_fwd_points_batch: bad size");
-  int rc = field_batch(dims, views, n_scenes, packed, tables, &a, n_points, "avr_field_fwd_points_batch");
+  int rc = field_batch(dims, views, n_scenes, packed, tables, &a, n_points, "avr_field_fwd_points_batch", true);
   if (rc) return rc;
   AVR_REQUIRE(n_points == 0 || (xyz && viewdirs && out), "avr_field_fwd_points_batch: null pointer");
   a.xyz = xyz; a.vd = viewdirs; a.n_samples = 1;
   a.out = reinterpret_cast<float4*>(out);
   if (a.M == 0) return AVR_OK;
-  return dispatch_field_x3(dims->d_hidden, a, as_stream(stream));
+  return dispatch_field(dims, a, as_stream(stream));
 }
 
 extern "C" int avr_field_fwd_points_split(const avr_field_dims* dims, const avr_view_desc* views, int n_scenes,
@@ -532,6 +552,8 @@ extern "C" int avr_field_fwd_points_split(const avr_field_dims* dims, const avr_
                                           const float* viewdirs, int64_t n_points, int b_begin, int b_end,
                                           const float* h_in, float* h_out, float* out, void* stream) {
   FieldArgs a{};
+  if (dims && dims->precision == AVR_FIELD_FP16)
+    return fail(AVR_E_UNSUPPORTED, "avr_field_fwd_points_split: AVR_FIELD_FP16 has no split (NS > 1) launch");
   AVR_REQUIRE(n_points >= 0, "avr_field_fwd_points_split: bad size");
   int rc = field_batch(dims, views, n_scenes, packed, tables, &a, n_points, "avr_field_fwd_points_split");
   if (rc) return rc;

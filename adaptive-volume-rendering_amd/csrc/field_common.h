@@ -353,6 +353,8 @@ inline bool env_eight_waves(const char* name) {
 int dispatch_field_x3(int d_hidden, const FieldArgs& a, hipStream_t s);
 // The same over a.M = capacity rows with the row count read from *a.count on the device (ReLU inference nets)
 int dispatch_field_x3_counted(int d_hidden, const FieldArgs& a, hipStream_t s);
+// AVR_FIELD_FP16: the single-product kernels on the x3 blob (ReLU inference, whole passes; a.count: counted)
+int dispatch_field_fp16(int d_hidden, const FieldArgs& a, hipStream_t s);
 // The packed blobs' layouts for dims (field_pack.hip; both check dims), for the entry points and the kernels of
 // other units (bn_train.hip: the layer-by-layer BatchNorm training GEMMs read the same fragments).
 int field_layout(const avr_field_dims* d, Layout* L);

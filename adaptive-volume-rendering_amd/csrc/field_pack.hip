@@ -330,7 +330,7 @@ extern "C" int avr_field_pack(const avr_field_dims* dims, const avr_resnetfc_wei
   const int H = dims->d_hidden, NT = L.NT;
   // the fp32 fragments the x3 kernels never read (lin_in, fc_0, fc_1) are packed only for an fp32 blob; the
   // lin_z / scale_z ones always (the exact-fp32 tables)
-  const bool fp32 = dims->precision != AVR_FIELD_X3;
+  const bool fp32 = dims->precision != AVR_FIELD_X3 && dims->precision != AVR_FIELD_FP16;
   LinBatch lb{};
   BiasBatch bb{};
   if (fp32 && (rc = pack_linear(w->lin_in_w, H, dims->d_in, NT, kInTiles, packed + L.w_in, lb))) return rc;
@@ -380,7 +380,8 @@ extern "C" int avr_field_pack(const avr_field_dims* dims, const avr_resnetfc_wei
       return rc;
   }
   if ((rc = run_x3(bt, s))) return rc;
-  record_pack(packed, dims->precision);
+  // (AVR_FIELD_FP16 packs what AVR_FIELD_X3 packs: recorded as that)
+  record_pack(packed, dims->precision == AVR_FIELD_FP16 ? AVR_FIELD_X3 : dims->precision);
   return AVR_OK;
 }
 

@@ -231,9 +231,15 @@ __device__ __forceinline__ void save_layer(const FieldArgs& a, int layer, const 
 // count M read from a.count on the device by a wave-uniform load. A workgroup whose first row is at or beyond it
 // leaves before its first barrier, LDS write or s_setprio; the last live one clamps and guards its tail rows
 // against M as the uncounted kernel does against a.M.
-template <int FT, int NW, bool SAVE, bool BN = false, bool SPADE = false, int ACT = 0, bool CNT = false>
+// NP (AVR_FIELD_FP16: NP = 1; ReLU inference, whole passes): the products per GEMM term. 3 is the x3 arithmetic
+// above; 1 keeps Wh.xh alone in every layer (lin_in, fc_0, fc_1, lin_out): one MFMA per (tile, sample group,
+// K-chunk), only the hi half of each weight fragment loaded, only hi = fp16(x * s_x) (round to nearest even)
+// written to and read from X, under the same scales, from the same blob. The lin_z blend stays fp32.
+template <int FT, int NW, bool SAVE, bool BN = false, bool SPADE = false, int ACT = 0, bool CNT = false, int NP = 3>
 __global__ void __launch_bounds__(64 * NW, 1) field_x3_kernel(FieldArgs a) {
   static_assert(!CNT || (!SAVE && !BN && !SPADE && ACT == 0), "counted: ReLU inference only");
+  static_assert(NP == 3 || (NP == 1 && !SAVE && !BN && !SPADE && ACT == 0), "single product: ReLU inference only");
+  using Frag = FragT<NP>;
   int64_t counted = 0;
   if constexpr (CNT) {
     counted = counted_rows(a);
@@ -287,7 +293,7 @@ __global__ void __launch_bounds__(64 * NW, 1) field_x3_kernel(FieldArgs a) {
   const uint4* P16 = reinterpret_cast<const uint4*>(a.packed);  // 16-B units
 
   floatx4 h[FT][4], t[FT][4], v[FT][4];
-  FragX3 A0[FT];   // chunk 0 of the next GEMM's weights, prefetched before the publish ahead of it
+  Frag A0[FT];   // chunk 0 of the next GEMM's weights, prefetched before the publish ahead of it
   float S_h = 1.0f, s_x = 1.0f, mx = 0.f;
   // 8 waves: stage rows of the next lin_z table that are already in flight
   // ([p0, p1), issued while the preceding GEMM still read other parts of X)
@@ -386,7 +392,8 @@ __global__ void __launch_bounds__(64 * NW, 1) field_x3_kernel(FieldArgs a) {
         const float y = val * s_x;
         const _Float16 hi = (_Float16)y;
         *reinterpret_cast<_Float16*>(xb + xidx(c, 0, gg, s) * 16 + 2 * e) = hi;
-        *reinterpret_cast<_Float16*>(xb + xidx(c, 1, gg, s) * 16 + 2 * e) = (_Float16)(y - (float)hi);
+        if constexpr (NP == 3)
+          *reinterpret_cast<_Float16*>(xb + xidx(c, 1, gg, s) * 16 + 2 * e) = (_Float16)(y - (float)hi);
       };
 #pragma unroll
       for (int i = 0; i < PES; ++i)
@@ -504,7 +511,7 @@ __global__ void __launch_bounds__(64 * NW, 1) field_x3_kernel(FieldArgs a) {
       else if constexpr (SAVE)
         s_x = publish_affine_save<FT, NW, false>(X16, h, 1.0f / S_h, bz, mx, red, wid, lane, g, j, a, 2 * b, base,
                                                  roff, &tail->lmax[2 * b]);
-      else s_x = publish_affine<FT, NW, false, ACT>(X16, h, 1.0f / S_h, bz, mx, red, wid, lane, g, j, beta);
+      else s_x = publish_affine<FT, NW, false, ACT, NP>(X16, h, 1.0f / S_h, bz, mx, red, wid, lane, g, j, beta);
       AVR_STAMP(6 + 5 * (b & 3));
       const float S_t = layer_scale(a.packed, L, 2 + 2 * b) * s_x;
       gemm<FT, true, TWO>(t, A0, W0, KC, 64 * NTT, X16, lane);
@@ -520,7 +527,7 @@ __global__ void __launch_bounds__(64 * NW, 1) field_x3_kernel(FieldArgs a) {
       if constexpr (SAVE)
         s_x = publish_affine_save<FT, NW, true>(X16, t, 1.0f / S_t, bv, mx, red, wid, lane, g, j, a, 2 * b + 1, base,
                                                 roff, &tail->lmax[2 * b + 1]);
-      else s_x = publish_affine<FT, NW, true, ACT>(X16, t, 1.0f / S_t, bv, mx, red, wid, lane, g, j, beta);
+      else s_x = publish_affine<FT, NW, true, ACT, NP>(X16, t, 1.0f / S_t, bv, mx, red, wid, lane, g, j, beta);
       AVR_STAMP(8 + 5 * (b & 3));
       // fc_1 accumulates onto the residual, rescaled to this layer's scale (+ b1)
       const float S1 = layer_scale(a.packed, L, 3 + 2 * b) * s_x;
@@ -533,7 +540,7 @@ __global__ void __launch_bounds__(64 * NW, 1) field_x3_kernel(FieldArgs a) {
       gemm<FT, false, TWO>(h, A0, W1, KC, 64 * NTT, X16, lane);
     } else {
       if (SAVE) save_layer<FT, NW>(a, 2 * b, v, base, roff, wid, g, j, lane);
-      s_x = publish<FT, NW>(X16, v, mx, red, wid, lane, g, j, SAVE ? &tail->lmax[2 * b] : nullptr);
+      s_x = publish<FT, NW, NP>(X16, v, mx, red, wid, lane, g, j, SAVE ? &tail->lmax[2 * b] : nullptr);
       AVR_STAMP(6 + 5 * (b & 3));
       // fc_0 (from zero)
       const float S_t = layer_scale(a.packed, L, 2 + 2 * b) * s_x;
@@ -543,7 +550,7 @@ __global__ void __launch_bounds__(64 * NW, 1) field_x3_kernel(FieldArgs a) {
       mx = act_bound<ACT>(prep_input<FT, true, ACT>(v, t, 1.0f / S_t, a.packed + L.b_fc0[b], wid, g, beta), beta);
       prefetch_a<FT, NPF>(A0, W1, lane);
       if (SAVE) save_layer<FT, NW>(a, 2 * b + 1, v, base, roff, wid, g, j, lane);
-      s_x = publish<FT, NW>(X16, v, mx, red, wid, lane, g, j, SAVE ? &tail->lmax[2 * b + 1] : nullptr);
+      s_x = publish<FT, NW, NP>(X16, v, mx, red, wid, lane, g, j, SAVE ? &tail->lmax[2 * b + 1] : nullptr);
       AVR_STAMP(8 + 5 * (b & 3));
       // fc_1 accumulates onto the residual, rescaled to this layer's scale (+ b1)
       const float S1 = layer_scale(a.packed, L, 3 + 2 * b) * s_x;
@@ -584,9 +591,9 @@ __global__ void __launch_bounds__(64 * NW, 1) field_x3_kernel(FieldArgs a) {
     // scale, the partials meet in LDS (the dead dedup area of the tail) and waves 0-3
     // sum them in wave order for samples 16w + j.
     const uint4* wo = P16 + L.x3_out / 4 + lane;
-    FragX3 Aw[2];
+    Frag Aw[2];
 #pragma unroll
-    for (int cc = 0; cc < 2; ++cc) Aw[cc] = load_frag(wo + 2 * 64 * (2 * wid + cc));
+    for (int cc = 0; cc < 2; ++cc) Aw[cc] = load_frag_as<Frag>(wo + 2 * 64 * (2 * wid + cc));
     const float f = 1.0f / S_h;
     const float mxw = act_bound<ACT>(max_relu_affine<FT, false>(h, f, bz), beta);
     const float s_w = pow2_scale_for(mxw);
@@ -623,14 +630,20 @@ __global__ void __launch_bounds__(64 * NW, 1) field_x3_kernel(FieldArgs a) {
             set_mask_bits(sbits, y, ft, sg);
           }
         }
-        split4(y0, s_w, h0, l0);
-        if constexpr (!SAVE) y1 = relu_affine<false, ACT>(h[2 * cc + 1][sg], f, bz[0], beta);
-        split4(y1, s_w, h1, l1);
-        const half8 bh = __builtin_bit_cast(half8, make_uint4(h0.x, h0.y, h1.x, h1.y));
-        const half8 bl = __builtin_bit_cast(half8, make_uint4(l0.x, l0.y, l1.x, l1.y));
-        part[sg] = mfma32h(Aw[cc].hi, bh, part[sg]);
-        part[sg] = mfma32h(Aw[cc].hi, bl, part[sg]);
-        part[sg] = mfma32h(Aw[cc].lo, bh, part[sg]);
+        if constexpr (NP == 3) {
+          split4(y0, s_w, h0, l0);
+          if constexpr (!SAVE) y1 = relu_affine<false, ACT>(h[2 * cc + 1][sg], f, bz[0], beta);
+          split4(y1, s_w, h1, l1);
+          const half8 bh = __builtin_bit_cast(half8, make_uint4(h0.x, h0.y, h1.x, h1.y));
+          const half8 bl = __builtin_bit_cast(half8, make_uint4(l0.x, l0.y, l1.x, l1.y));
+          part[sg] = mfma32h(Aw[cc].hi, bh, part[sg]);
+          part[sg] = mfma32h(Aw[cc].hi, bl, part[sg]);
+          part[sg] = mfma32h(Aw[cc].lo, bh, part[sg]);
+        } else {   // one product: the hi halves alone
+          h0 = round4(y0, s_w);
+          h1 = round4(relu_affine<false, ACT>(h[2 * cc + 1][sg], f, bz[0], beta), s_w);
+          part[sg] = mfma32h(Aw[cc].hi, __builtin_bit_cast(half8, make_uint4(h0.x, h0.y, h1.x, h1.y)), part[sg]);
+        }
       }
     }
     const float un = 1.0f / (layer_scale(a.packed, L, 1) * s_w);
@@ -674,19 +687,19 @@ __global__ void __launch_bounds__(64 * NW, 1) field_x3_kernel(FieldArgs a) {
   }
   // ---- lin_out(relu(h)): waves 0-3 compute the 16-row output tile for samples 16w + j.
   // (a quarter of lin_out's A fragments are loaded ahead of the publish, the rest after)
-  FragX3 Ao[KC];
+  Frag Ao[KC];
   const uint4* wo = P16 + L.x3_out / 4;
   const unsigned wlo = lane;
   if (wid < 4) {
 #pragma unroll
-    for (int c = 0; c < KC / 4; ++c) Ao[c] = load_frag(wo + (wlo + 2 * 64 * c));
+    for (int c = 0; c < KC / 4; ++c) Ao[c] = load_frag_as<Frag>(wo + (wlo + 2 * 64 * c));
   }
   mx = act_bound<ACT>(prep_input<FT, false, ACT>(v, h, 1.0f / S_h, nullptr, wid, g, beta), beta);
   if (SAVE) save_layer<FT, NW>(a, 2 * a.n_blocks, v, base, roff, wid, g, j, lane);
-  s_x = publish<FT, NW>(X16, v, mx, red, wid, lane, g, j, SAVE ? &tail->lmax[2 * a.n_blocks] : nullptr);
+  s_x = publish<FT, NW, NP>(X16, v, mx, red, wid, lane, g, j, SAVE ? &tail->lmax[2 * a.n_blocks] : nullptr);
   if (wid < 4) {
 #pragma unroll
-    for (int c = KC / 4; c < KC; ++c) Ao[c] = load_frag(wo + (wlo + 2 * 64 * c));
+    for (int c = KC / 4; c < KC; ++c) Ao[c] = load_frag_as<Frag>(wo + (wlo + 2 * 64 * c));
   }
   AVR_STAMP(25);
   if (wid >= 4) return;
@@ -697,10 +710,12 @@ __global__ void __launch_bounds__(64 * NW, 1) field_x3_kernel(FieldArgs a) {
 #pragma unroll
     for (int c = 0; c < KC; ++c) {
       const half8 bh = __builtin_bit_cast(half8, X16[xidx(c, 0, g, s)]);
-      const half8 bl = __builtin_bit_cast(half8, X16[xidx(c, 1, g, s)]);
       o = mfma32h(Ao[c].hi, bh, o);
-      o = mfma32h(Ao[c].hi, bl, o);
-      o = mfma32h(Ao[c].lo, bh, o);
+      if constexpr (NP == 3) {
+        const half8 bl = __builtin_bit_cast(half8, X16[xidx(c, 1, g, s)]);
+        o = mfma32h(Ao[c].hi, bl, o);
+        o = mfma32h(Ao[c].lo, bh, o);
+      }
     }
   }
   o *= 1.0f / S;
@@ -830,13 +845,13 @@ int dispatch_table_x3(const float* packed, const Layout& L, const float* latent,
   });
 }
 
-template <int FT, int NW, bool SAVE, bool BN = false, bool SPADE = false, int ACT = 0, bool CNT = false>
+template <int FT, int NW, bool SAVE, bool BN = false, bool SPADE = false, int ACT = 0, bool CNT = false, int NP = 3>
 static int launch_x3(const FieldArgs& a, hipStream_t s) {
   const size_t shm = LdsPlan<16 * FT * NW>::BYTES;
   const int64_t blocks = (SAVE || a.n_scenes > 1) ? a.blocks_per_scene * a.n_scenes
                                                   : (a.M + kX3Samples - 1) / kX3Samples;
-  return launch_lds<field_x3_kernel<FT, NW, SAVE, BN, SPADE, ACT, CNT>>("field_x3_kernel", "field: too many points",
-                                                                        blocks, 1, 1, 64 * NW, shm, shm, s, a);
+  return launch_lds<field_x3_kernel<FT, NW, SAVE, BN, SPADE, ACT, CNT, NP>>(
+      "field_x3_kernel", "field: too many points", blocks, 1, 1, 64 * NW, shm, shm, s, a);
 }
 
 // d_hidden 512 runs 8 waves x 4 tiles where the variant has that layout (inference: +2.7-4.7 % over the 4-wave
@@ -879,6 +894,24 @@ int dispatch_field_x3_counted(int d_hidden, const FieldArgs& a, hipStream_t s) {
               "field x3 counted: single-scene ReLU inference only");
   return x3_width<0>(d_hidden, env_eight_waves("AVR_X3_WAVES"), "field x3 counted", [&](auto ft, auto nw) {
     return launch_x3<decltype(ft)::value, decltype(nw)::value, false, false, false, 0, true>(a, s);
+  });
+}
+
+// AVR_FIELD_FP16: the single-product kernels (field_x3_kernel<..., NP = 1>) for ReLU nets without BatchNorm,
+// use_spade and Softplus, whole passes (no split halves), inference; a.count set: the counted launch. The same
+// layouts and the same AVR_X3_WAVES switch as the x3 inference kernels.
+int dispatch_field_fp16(int d_hidden, const FieldArgs& a, hipStream_t s) {
+  if (a.L.bn || a.L.spade || a.beta > 0.f)
+    return fail(AVR_E_UNSUPPORTED, "field fp16: BatchNorm, use_spade and Softplus nets have no single-product kernel "
+                                   "(AVR_FIELD_X3 runs them)");
+  if (a.h_in || a.h_out)
+    return fail(AVR_E_UNSUPPORTED, "field fp16: no split (NS > 1) launch");
+  AVR_REQUIRE(!a.act, "field fp16: inference only");
+  AVR_REQUIRE(!a.count || a.n_scenes <= 1, "field fp16 counted: single scene");
+  return x3_width<0>(d_hidden, env_eight_waves("AVR_X3_WAVES"), "field fp16", [&](auto ft, auto nw) {
+    constexpr int FT = decltype(ft)::value, NW = decltype(nw)::value;
+    return a.count ? launch_x3<FT, NW, false, false, false, 0, true, 1>(a, s)
+                   : launch_x3<FT, NW, false, false, false, 0, false, 1>(a, s);
   });
 }
 

@@ -35,11 +35,49 @@ struct BPair {
   half8 hi, lo;
 };
 
+// Single-product operands (the "fp16" inference precision, AVR_FIELD_FP16): the hi halves alone, W.x ~= Wh.xh,
+// from the same blob and the same LDS slots (the lo halves are neither loaded, written nor read). A GEMM
+// building block takes its product count from its fragment type: FragX3 / BPair three products, FragH / BOne one.
+struct FragH {
+  half8 hi;
+};
+struct BOne {
+  half8 hi;
+};
+template <int NP>
+using FragT = std::conditional_t<NP == 3, FragX3, FragH>;
+template <typename F>
+using BOf = std::conditional_t<std::is_same_v<F, FragX3>, BPair, BOne>;
+template <typename F>
+constexpr int kProducts = std::is_same_v<F, FragX3> ? 3 : 1;
+
+template <typename F>
+__device__ __forceinline__ F load_frag_as(const uint4* p) {
+  if constexpr (std::is_same_v<F, FragX3>) {
+    return load_frag(p);
+  } else {
+    FragH f;
+    f.hi = __builtin_bit_cast(half8, p[0]);
+    return f;
+  }
+}
+
 __device__ __forceinline__ BPair read_b(const uint4* X16, int c, int sg, int g, int j) {
   BPair b;
   b.hi = __builtin_bit_cast(half8, X16[xidx(c, 0, g, 16 * sg + j)]);
   b.lo = __builtin_bit_cast(half8, X16[xidx(c, 1, g, 16 * sg + j)]);
   return b;
+}
+
+template <typename B>
+__device__ __forceinline__ B read_b_as(const uint4* X16, int c, int sg, int g, int j) {
+  if constexpr (std::is_same_v<B, BPair>) {
+    return read_b(X16, c, sg, g, j);
+  } else {
+    BOne b;
+    b.hi = __builtin_bit_cast(half8, X16[xidx(c, 0, g, 16 * sg + j)]);
+    return b;
+  }
 }
 
 // hi = fp16(x*s), lo = fp16(x*s - hi): one packed convert per pair for hi and
@@ -55,6 +93,15 @@ __device__ __forceinline__ void split4(const floatx4& x, float s, uint2& hi, uin
   asm("v_fma_mixhi_f16 %0, %1, %2, -%3 op_sel:[0,0,1] op_sel_hi:[0,0,1]" : "+v"(l1) : "v"(x.w), "v"(s), "v"(h1));
   hi = make_uint2(h0, h1);
   lo = make_uint2(l0, l1);
+}
+
+// hi alone (single product): fp16(x*s), round to nearest even, the same packed convert
+__device__ __forceinline__ uint2 round4(const floatx4& x, float s) {
+  const floatx4 y = x * s;
+  unsigned h0, h1;
+  asm("v_cvt_pk_f16_f32 %0, %1, %2" : "=v"(h0) : "v"(y.x), "v"(y.y));
+  asm("v_cvt_pk_f16_f32 %0, %1, %2" : "=v"(h1) : "v"(y.z), "v"(y.w));
+  return make_uint2(h0, h1);
 }
 
 // Side task of a GEMM (the backward kernel, RowSideH): copy the GEMM's own operand X out of
@@ -127,30 +174,33 @@ struct RowSideH : RowSide {
 // last pair each B[sg] is refilled with the next chunk's fragment as soon as
 // its MFMAs have issued. The side task reads its slots of chunk cc in pair 0
 // and converts / stores them in pair 1 (in pair 0's tail for a single pair).
-template <int FT, bool ZERO, typename Side = NoSide>
-__device__ __forceinline__ void chunk_step(floatx4 (&acc)[FT][4], const FragX3 (&A)[FT], FragX3 (&An)[FT],
-                                           const uint4* wn, BPair (&B)[4], const uint4* X16, int cn, int g, int j,
+template <int FT, bool ZERO, typename Side = NoSide, typename F = FragX3>
+__device__ __forceinline__ void chunk_step(floatx4 (&acc)[FT][4], const F (&A)[FT], F (&An)[FT],
+                                           const uint4* wn, BOf<F> (&B)[4], const uint4* X16, int cn, int g, int j,
                                            Side& side, int cc) {
+  constexpr int NP = kProducts<F>;
   constexpr int GS = FT >= 2 ? 2 : 1;       // tiles per group
   constexpr int NG = FT / GS;
-  constexpr int NMF = 3 * GS * 4;           // MFMAs per group
-  constexpr int NLD = 2 * GS;               // global loads per group
+  constexpr int NMF = NP * GS * 4;          // MFMAs per group
+  constexpr int NLD = (NP == 3 ? 2 : 1) * GS;   // global loads per group
   constexpr int PER = NMF / (NLD + 1);
 #pragma unroll
   for (int p = 0; p < NG; ++p) {
     if (p == 0) side.load(X16, cc);
 #pragma unroll
-    for (int q = 0; q < GS; ++q) An[GS * p + q] = load_frag(wn + 2 * 64 * (GS * p + q));
+    for (int q = 0; q < GS; ++q) An[GS * p + q] = load_frag_as<F>(wn + 2 * 64 * (GS * p + q));
 #pragma unroll
     for (int sg = 0; sg < 4; ++sg) {
 #pragma unroll
       for (int q = 0; q < GS; ++q) {
         const int ft = GS * p + q;
         acc[ft][sg] = mfma32h(A[ft].hi, B[sg].hi, ZERO ? floatx4{0.f, 0.f, 0.f, 0.f} : acc[ft][sg]);
-        acc[ft][sg] = mfma32h(A[ft].hi, B[sg].lo, acc[ft][sg]);
-        acc[ft][sg] = mfma32h(A[ft].lo, B[sg].hi, acc[ft][sg]);
+        if constexpr (NP == 3) {
+          acc[ft][sg] = mfma32h(A[ft].hi, B[sg].lo, acc[ft][sg]);
+          acc[ft][sg] = mfma32h(A[ft].lo, B[sg].hi, acc[ft][sg]);
+        }
       }
-      if (p == NG - 1) B[sg] = read_b(X16, cn, sg, g, j);
+      if (p == NG - 1) B[sg] = read_b_as<BOf<F>>(X16, cn, sg, g, j);
     }
 #pragma unroll
     for (int i = 0; i < NLD; ++i) {
@@ -175,24 +225,24 @@ __device__ __forceinline__ void chunk_step(floatx4 (&acc)[FT][4], const FragX3 (
 // (The 8-wave layout, 4 tiles per wave, prefetches all of them: NPF = FT.)
 constexpr int kPrefetch = 2;
 
-template <int FT, int NPF = kPrefetch>
-__device__ __forceinline__ void prefetch_a(FragX3 (&A0)[FT], const uint4* __restrict__ W, int lane) {
+template <int FT, int NPF = kPrefetch, typename F = FragX3>
+__device__ __forceinline__ void prefetch_a(F (&A0)[FT], const uint4* __restrict__ W, int lane) {
 #pragma unroll
-  for (int ft = 0; ft < (FT < NPF ? FT : NPF); ++ft) A0[ft] = load_frag(W + (unsigned)(lane + 2 * 64 * ft));
+  for (int ft = 0; ft < (FT < NPF ? FT : NPF); ++ft) A0[ft] = load_frag_as<F>(W + (unsigned)(lane + 2 * 64 * ft));
 }
 
 // A0 holds chunk 0 (prefetch_a). side: an optional side task per K-chunk (RowSide).
-template <int FT, bool ZERO, bool SYNC, typename Side = NoSide>
-__device__ __forceinline__ void gemm_x3(floatx4 (&acc)[FT][4], FragX3 (&A0)[FT], const uint4* __restrict__ W, int KC,
+template <int FT, bool ZERO, bool SYNC, typename Side = NoSide, typename F = FragX3>
+__device__ __forceinline__ void gemm_x3(floatx4 (&acc)[FT][4], F (&A0)[FT], const uint4* __restrict__ W, int KC,
                                         int cstride, const uint4* X16, int lane, Side side = Side{}) {
   const int g = lane >> 4, j = lane & 15;
   const uint4* wl = W + lane;
-  FragX3 A1[FT];
-  BPair B[4];
+  F A1[FT];
+  BOf<F> B[4];
 #pragma unroll
-  for (int ft = kPrefetch; ft < FT; ++ft) A0[ft] = load_frag(wl + 2 * 64 * ft);
+  for (int ft = kPrefetch; ft < FT; ++ft) A0[ft] = load_frag_as<F>(wl + 2 * 64 * ft);
 #pragma unroll
-  for (int sg = 0; sg < 4; ++sg) B[sg] = read_b(X16, 0, sg, g, j);
+  for (int sg = 0; sg < 4; ++sg) B[sg] = read_b_as<BOf<F>>(X16, 0, sg, g, j);
   __builtin_amdgcn_sched_barrier(0);
   for (int c = 0; c < KC; c += 2) {
     const int c2 = c + 2 < KC ? c + 2 : c + 1;
@@ -217,28 +267,39 @@ __device__ __forceinline__ void gemm_x3(floatx4 (&acc)[FT][4], FragX3 (&A0)[FT],
 // during sample group sg (FT == 4: one tile per group). The side task (the
 // backward chain's G rows, RowSide8) reads its slots of chunk c in sample
 // group 0 and stores its rows in sample group 2.
-template <int FT, bool ZERO, typename Side = NoSide>
-__device__ __forceinline__ void chunk_step_sg(floatx4 (&acc)[FT][4], const FragX3 (&A)[FT], FragX3 (&An)[FT],
-                                              const uint4* __restrict__ wn, unsigned lo, BPair& B, const uint4* X16,
+template <int FT, bool ZERO, typename Side = NoSide, typename F = FragX3>
+__device__ __forceinline__ void chunk_step_sg(floatx4 (&acc)[FT][4], const F (&A)[FT], F (&An)[FT],
+                                              const uint4* __restrict__ wn, unsigned lo, BOf<F>& B, const uint4* X16,
                                               int c, int cn, int g, int j, Side& side) {
   static_assert(FT == 4, "one next-chunk tile per sample group");
+  constexpr int NP = kProducts<F>;
 #pragma unroll
   for (int sg = 0; sg < 4; ++sg) {
     if (sg == 0) side.load(X16, c);
-    const BPair Bn = sg < 3 ? read_b(X16, c, sg + 1, g, j) : read_b(X16, cn, 0, g, j);
-    An[sg] = load_frag(wn + (lo + 2 * 64 * sg));   // wave-uniform base + 32-bit lane offset
+    const BOf<F> Bn = sg < 3 ? read_b_as<BOf<F>>(X16, c, sg + 1, g, j) : read_b_as<BOf<F>>(X16, cn, 0, g, j);
+    An[sg] = load_frag_as<F>(wn + (lo + 2 * 64 * sg));   // wave-uniform base + 32-bit lane offset
 #pragma unroll
     for (int ft = 0; ft < FT; ++ft) {
       acc[ft][sg] = mfma32h(A[ft].hi, B.hi, ZERO ? floatx4{0.f, 0.f, 0.f, 0.f} : acc[ft][sg]);
-      acc[ft][sg] = mfma32h(A[ft].hi, B.lo, acc[ft][sg]);
-      acc[ft][sg] = mfma32h(A[ft].lo, B.hi, acc[ft][sg]);
+      if constexpr (NP == 3) {
+        acc[ft][sg] = mfma32h(A[ft].hi, B.lo, acc[ft][sg]);
+        acc[ft][sg] = mfma32h(A[ft].lo, B.hi, acc[ft][sg]);
+      }
     }
     if (sg == 2) side.store(c);
-    __builtin_amdgcn_sched_group_barrier(0x008, 4, 0);
-    __builtin_amdgcn_sched_group_barrier(0x020, 2, 0);
-    __builtin_amdgcn_sched_group_barrier(0x008, 4, 0);
-    __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
-    __builtin_amdgcn_sched_group_barrier(0x008, 4, 0);
+    if constexpr (NP == 3) {
+      __builtin_amdgcn_sched_group_barrier(0x008, 4, 0);
+      __builtin_amdgcn_sched_group_barrier(0x020, 2, 0);
+      __builtin_amdgcn_sched_group_barrier(0x008, 4, 0);
+      __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
+      __builtin_amdgcn_sched_group_barrier(0x008, 4, 0);
+    } else {   // 4 MFMAs, one weight load, one LDS read
+      __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+      __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
+      __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
+      __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+      __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+    }
     __builtin_amdgcn_sched_barrier(0);
     B = Bn;
   }
@@ -246,15 +307,15 @@ __device__ __forceinline__ void chunk_step_sg(floatx4 (&acc)[FT][4], const FragX
 
 // A0 holds chunk 0's first NPF tiles (prefetch_a<FT, NPF>). No barrier in the
 // loop: the two waves of a SIMD drift apart by priority (field_x3_kernel).
-template <int FT, bool ZERO, int NPF = FT, typename Side = NoSide>
-__device__ __forceinline__ void gemm_x3_sg(floatx4 (&acc)[FT][4], FragX3 (&A0)[FT], const uint4* __restrict__ W,
+template <int FT, bool ZERO, int NPF = FT, typename Side = NoSide, typename F = FragX3>
+__device__ __forceinline__ void gemm_x3_sg(floatx4 (&acc)[FT][4], F (&A0)[FT], const uint4* __restrict__ W,
                                            int KC, int cstride, const uint4* X16, int lane, Side side = Side{}) {
   const int g = lane >> 4, j = lane & 15;
   const unsigned lo = lane;          // W (wave-uniform) + lo: this lane's fragment
-  FragX3 A1[FT];
+  F A1[FT];
 #pragma unroll
-  for (int ft = NPF; ft < FT; ++ft) A0[ft] = load_frag(W + (lo + 2 * 64 * ft));
-  BPair B = read_b(X16, 0, 0, g, j);
+  for (int ft = NPF; ft < FT; ++ft) A0[ft] = load_frag_as<F>(W + (lo + 2 * 64 * ft));
+  BOf<F> B = read_b_as<BOf<F>>(X16, 0, 0, g, j);
   __builtin_amdgcn_sched_barrier(0);
   for (int c = 0; c < KC; c += 2) {
     const int c2 = c + 2 < KC ? c + 2 : c + 1;
@@ -271,8 +332,8 @@ __device__ __forceinline__ void gemm_x3_sg(floatx4 (&acc)[FT][4], FragX3 (&A0)[F
 // The K loop of one layer in a kernel's layout: 8 waves (TWO) run gemm_x3_sg on a fully prefetched chunk 0,
 // 4 waves gemm_x3 without its barrier. (The backward kernel, whose GEMMs carry a side task, calls the two
 // directly: passing the task through this selector changed field_bwd_x3_kernel<2, 4, *>'s code.)
-template <int FT, bool ZERO, bool TWO>
-__device__ __forceinline__ void gemm(floatx4 (&acc)[FT][4], FragX3 (&A0)[FT], const uint4* __restrict__ W, int KC,
+template <int FT, bool ZERO, bool TWO, typename F = FragX3>
+__device__ __forceinline__ void gemm(floatx4 (&acc)[FT][4], F (&A0)[FT], const uint4* __restrict__ W, int KC,
                                      int cstride, const uint4* X16, int lane) {
   if constexpr (TWO)
     gemm_x3_sg<FT, ZERO, FT>(acc, A0, W, KC, cstride, X16, lane);
@@ -363,7 +424,7 @@ __device__ __forceinline__ float prep_input(floatx4 (&v)[FT][4], const floatx4 (
 }
 
 // X <- split(v * s_x) for this wave's feature tiles
-template <int FT>
+template <int FT, int NP = 3>
 __device__ __forceinline__ void store_split(uint4* X16, const floatx4 (&v)[FT][4], float s_x, int wid, int g, int j) {
   char* base = reinterpret_cast<char*>(X16);
 #pragma unroll
@@ -371,11 +432,16 @@ __device__ __forceinline__ void store_split(uint4* X16, const floatx4 (&v)[FT][4
     const int ftg = FT * wid + ft;
 #pragma unroll
     for (int sg = 0; sg < 4; ++sg) {
-      uint2 hi, lo;
-      split4(v[ft][sg], s_x, hi, lo);
-      const int s = 16 * sg + j;
-      *reinterpret_cast<uint2*>(base + xidx(ftg >> 1, 0, g, s) * 16 + (ftg & 1) * 8) = hi;
-      *reinterpret_cast<uint2*>(base + xidx(ftg >> 1, 1, g, s) * 16 + (ftg & 1) * 8) = lo;
+      if constexpr (NP == 3) {
+        uint2 hi, lo;
+        split4(v[ft][sg], s_x, hi, lo);
+        const int s = 16 * sg + j;
+        *reinterpret_cast<uint2*>(base + xidx(ftg >> 1, 0, g, s) * 16 + (ftg & 1) * 8) = hi;
+        *reinterpret_cast<uint2*>(base + xidx(ftg >> 1, 1, g, s) * 16 + (ftg & 1) * 8) = lo;
+      } else {   // the hi half alone
+        const int s = 16 * sg + j;
+        *reinterpret_cast<uint2*>(base + xidx(ftg >> 1, 0, g, s) * 16 + (ftg & 1) * 8) = round4(v[ft][sg], s_x);
+      }
     }
   }
 }
@@ -411,7 +477,7 @@ __device__ __forceinline__ float max_relu_affine(const floatx4 (&acc)[FT][4], fl
 }
 
 // X <- split(act(acc * f + b) * s_x) for this wave's feature tiles
-template <int FT, bool BIAS, int ACT = 0>
+template <int FT, bool BIAS, int ACT = 0, int NP = 3>
 __device__ __forceinline__ void store_split_affine(uint4* X16, const floatx4 (&acc)[FT][4], float f,
                                                    const floatx4 (&bv)[FT], float s_x, int wid, int g, int j,
                                                    float beta = 0.f) {
@@ -421,11 +487,17 @@ __device__ __forceinline__ void store_split_affine(uint4* X16, const floatx4 (&a
     const int ftg = FT * wid + ft;
 #pragma unroll
     for (int sg = 0; sg < 4; ++sg) {
-      uint2 hi, lo;
-      split4(relu_affine<BIAS, ACT>(acc[ft][sg], f, bv[ft], beta), s_x, hi, lo);
-      const int s = 16 * sg + j;
-      *reinterpret_cast<uint2*>(base + xidx(ftg >> 1, 0, g, s) * 16 + (ftg & 1) * 8) = hi;
-      *reinterpret_cast<uint2*>(base + xidx(ftg >> 1, 1, g, s) * 16 + (ftg & 1) * 8) = lo;
+      if constexpr (NP == 3) {
+        uint2 hi, lo;
+        split4(relu_affine<BIAS, ACT>(acc[ft][sg], f, bv[ft], beta), s_x, hi, lo);
+        const int s = 16 * sg + j;
+        *reinterpret_cast<uint2*>(base + xidx(ftg >> 1, 0, g, s) * 16 + (ftg & 1) * 8) = hi;
+        *reinterpret_cast<uint2*>(base + xidx(ftg >> 1, 1, g, s) * 16 + (ftg & 1) * 8) = lo;
+      } else {   // the hi half alone
+        const int s = 16 * sg + j;
+        *reinterpret_cast<uint2*>(base + xidx(ftg >> 1, 0, g, s) * 16 + (ftg & 1) * 8) =
+            round4(relu_affine<BIAS, ACT>(acc[ft][sg], f, bv[ft], beta), s_x);
+      }
     }
   }
 }
@@ -495,7 +567,7 @@ __device__ __forceinline__ float red_max(const float* red) {
 // relu'd layer input -> LDS (two barriers: all reads of the previous X done /
 // all writes of the new X visible); returns the operand scale s_x
 // wgmax (training kernels): wave 0 records the workgroup's max there (LDS)
-template <int FT, int NW>
+template <int FT, int NW, int NP = 3>
 __device__ __forceinline__ float publish(uint4* X16, const floatx4 (&v)[FT][4], float mx, float* red, int wid,
                                          int lane, int g, int j, float* wgmax = nullptr) {
   if (lane == 0) red[wid] = mx;
@@ -503,7 +575,7 @@ __device__ __forceinline__ float publish(uint4* X16, const floatx4 (&v)[FT][4], 
   const float m = red_max<NW>(red);
   if (wgmax && wid == 0 && lane == 0) *wgmax = m;
   const float s_x = pow2_scale_for(m);
-  store_split<FT>(X16, v, s_x, wid, g, j);
+  store_split<FT, NP>(X16, v, s_x, wid, g, j);
   lds_barrier();
   return s_x;
 }
@@ -537,14 +609,14 @@ __device__ __forceinline__ float publish_bn(uint4* X16, const floatx4 (&acc)[FT]
 }
 
 // Two-pass publish of act(acc * f + b) (mx: a bound of the values, act_bound of max_relu_affine); returns s_x
-template <int FT, int NW, bool BIAS, int ACT = 0>
+template <int FT, int NW, bool BIAS, int ACT = 0, int NP = 3>
 __device__ __forceinline__ float publish_affine(uint4* X16, const floatx4 (&acc)[FT][4], float f,
                                                 const floatx4 (&bv)[FT], float mx, float* red, int wid, int lane,
                                                 int g, int j, float beta = 0.f) {
   if (lane == 0) red[wid] = mx;
   lds_barrier();
   const float s_x = pow2_scale_for(red_max<NW>(red));
-  store_split_affine<FT, BIAS, ACT>(X16, acc, f, bv, s_x, wid, g, j, beta);
+  store_split_affine<FT, BIAS, ACT, NP>(X16, acc, f, bv, s_x, wid, g, j, beta);
   lds_barrier();
   return s_x;
 }

@@ -185,7 +185,8 @@ typedef struct {
   int num_freqs;   /* positional-encoding frequencies                     */
   float freq_factor;
   int precision;   /* AVR_FIELD_FP32: v_mfma_f32_16x16x4_f32;
-                      AVR_FIELD_X3: split-fp16 v_mfma_f32_16x16x32_f16 (3 products, fp32 accumulate) */
+                      AVR_FIELD_X3: split-fp16 v_mfma_f32_16x16x32_f16 (3 products, fp32 accumulate);
+                      AVR_FIELD_FP16: the same MFMA, one product (inference only, see below)         */
   int bn;          /* 1: eval-mode BatchNorm in every block (train.py --bn, models.py:430-432, 456-461):
                       ResnetBlockFC applies bn_0 in front of BOTH relus (the reference's bn_0-twice quirk).
                       The caller folds the second one into fc_0 (fc0_w := diag(a) W0, fc0_b := a*b0 + c) and
@@ -203,6 +204,20 @@ typedef struct {
 
 #define AVR_FIELD_FP32 0
 #define AVR_FIELD_X3 1
+/* AVR_FIELD_FP16 (an addition within ABI 18): single-product fp16 MFMA for inference rendering. Every linear
+ * layer of the ResnetFC -- lin_in, fc_0 and fc_1 of every block, and lin_out -- keeps the one product Wh.xh of
+ * the three AVR_FIELD_X3 computes: operands rounded to fp16 (to nearest even) under the same power-of-two scales
+ * (s_w per layer from the blob header, s_x per layer and workgroup from the block's max), fp32 accumulation. The
+ * lin_z tables and their blend stay fp32. Not fp32-equivalent: about 1e-4 mean, 2e-3 max absolute error on rgb
+ * against the fp32 field at d_hidden 512, meant for 8-bit frames, never for training or parity.
+ *   - reads the AVR_FIELD_X3 blob byte for byte: avr_field_pack with AVR_FIELD_FP16 packs what AVR_FIELD_X3
+ *     packs, and the fp16 entries accept a blob packed for either;
+ *   - accepted by avr_field_fwd_rays, avr_field_fwd_points, their _batch forms and
+ *     avr_field_fwd_points_counted;
+ *   - AVR_E_UNSUPPORTED (never another path): a BatchNorm, use_spade or Softplus net, and
+ *     avr_field_fwd_points_split (NS > 1);
+ *   - the training, backward and table entries accept what they accepted before it existed. */
+#define AVR_FIELD_FP16 2
 
 /* One ResnetFC's nn.Linear tensors, PyTorch layout (out, in) row-major. */
 typedef struct {

@@ -1,11 +1,14 @@
 """Per-kernel comparison of the device assembly of two trees (diagnostic, CPU only).
 
-usage: python scripts/isa_compare.py PARENT_DIR TREE_DIR name [name ...]
+usage: python scripts/isa_compare.py [--added-default ARG] PARENT_DIR TREE_DIR name [name ...]
   (DIR/name.s from: hipcc <CXXFLAGS> --cuda-device-only -S csrc/name.hip -o DIR/name.s, as scripts/isa_stats.py)
 Kernels are matched by name and template arguments, not by the mangled parameter types (a renamed struct changes
 those and nothing else). Per kernel: the instruction counts, scratch bytes / SGPRs / VGPRs of both builds, and a
 verdict: identical text, the same instruction multiset in another order, the same opcode multiset with other
 registers or operands, or the opcodes whose counts differ.
+--added-default ARG (a mangled template argument, e.g. Li3): the tree gave kernels one more trailing template
+parameter whose default is ARG; a parent kernel K<args> is then compared with the tree's K<args, ARG>, and the
+tree's instantiations with another value of it are listed as new.
 """
 import collections
 import re
@@ -36,9 +39,24 @@ def opcodes(ins):
     return collections.Counter(i.split(" ")[0] for i in ins)
 
 
+def with_default(code, meta, parent, arg):
+    """The tree's K<args, arg> under the parent's key K<args> where the parent has that kernel."""
+    tail = f"E{arg}>"
+    for k in [k for k in code if k.endswith(tail) and k[:-len(tail)] + ">" in parent]:
+        code[k[:-len(tail)] + ">"] = code.pop(k)
+        if k in meta:
+            meta[k[:-len(tail)] + ">"] = meta.pop(k)
+
+
 def main():
-    for f in sys.argv[3:]:
-        (a, ma), (b, mb) = kernels(f"{sys.argv[1]}/{f}.s"), kernels(f"{sys.argv[2]}/{f}.s")
+    argv = sys.argv[1:]
+    added = None
+    if argv and argv[0] == "--added-default":
+        added, argv = argv[1], argv[2:]
+    for f in argv[2:]:
+        (a, ma), (b, mb) = kernels(f"{argv[0]}/{f}.s"), kernels(f"{argv[1]}/{f}.s")
+        if added:
+            with_default(b, mb, a, added)
         print(f"== {f}.hip")
         for k in sorted(set(a) | set(b)):
             if k not in a or k not in b:
