@@ -235,6 +235,11 @@ _SIGS = {
     "avr_occ_flag_sigma": [c_void_p, c_float, c_int, i64, c_void_p, c_void_p],
     "avr_occ_build_sparse": [c_void_p, c_void_p, c_void_p, i64, ctypes.POINTER(c_int), c_int, c_void_p, c_void_p],
     "avr_occ_downsample": [c_void_p, ctypes.POINTER(c_int), c_int, c_void_p, c_void_p],
+    "avr_occ_ray_bounds": [ctypes.POINTER(OccGrid), c_void_p, c_void_p, i64, c_float, c_float, c_void_p, c_void_p,
+                           c_void_p],
+    "avr_sample_coarse_bounds": [c_void_p, c_void_p, i64, c_int, c_void_p, u64, u64, c_void_p, c_void_p, c_void_p],
+    "avr_sample_fine_bounds": [c_void_p, c_void_p, c_void_p, c_void_p, i64, c_int, c_int, c_int, c_float, c_void_p,
+                               c_void_p, c_void_p, u64, u64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
     "avr_stream_copy": [c_void_p, c_void_p, i64, c_void_p],
     "avr_stream_fill": [c_void_p, i64, c_uint32, c_void_p],
 }

@@ -32,6 +32,10 @@ live counts. The graph's pool keeps the worst-case compacted buffers (40 B per s
 lives. A re-capture caused by a weight change meets the renderer's stale-grid ValueError, as an eager call would:
 rebuild the grid (OccupancyGrid.from_field), assign it to renderer.occupancy, then call refresh().
 
+Per-ray sampling bounds: `renderer.ray_bounds = "grid"` (with the gating above) is captured with the rest: the bounds
+launch per scene reads the grid's bits and the rays on the device and nothing is read back, so a replay bounds the
+rays it is given against the grid the bits hold then.
+
 Early termination: a renderer with `t_stop` set is accepted when `renderer.t_stop_count == "device"` (the fine pass's
 classify -> scan -> compact -> field -> composite chain per 64-sample chunk keeps every count on the device; the
 host-read mode is refused). With a grid set too, the coarse pass follows `occupancy_count`, which must then be
@@ -64,7 +68,7 @@ class GraphedRenderer:
         from .renderers import check_skip_modes
         check_skip_modes("GraphedRenderer: ", renderer.t_stop, getattr(renderer, "t_stop_count", "host"),
                          getattr(renderer, "occupancy", None), getattr(renderer, "occupancy_count", "host"),
-                         capture=True, name="renderer.{}".format)
+                         capture=True, name="renderer.{}".format, ray_bounds=getattr(renderer, "ray_bounds", None))
         if hasattr(renderer, "stage_host_draws") and renderer.seed is None:
             raise ValueError("GraphedRenderer: the adaptive renderers draw their start distances on the host "
                              "unless seeded (set renderer.seed)")

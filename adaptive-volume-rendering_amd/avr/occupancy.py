@@ -120,6 +120,27 @@ class OccupancyGrid:
         self.n_candidates, self.build_evals = other.n_candidates, other.build_evals
         return self
 
+    def ray_bounds(self, ro, rd, near, far, out=None):
+        """avr_occ_ray_bounds: ro, rd (..., 3) -> (t_near, t_far), each of ro's leading shape: where along [near, far]
+        (two floats, near < far) every sample of a ray that this grid calls live lies. A ray that clearly misses the
+        occupied cells, or has a non-finite component, gets exactly (near, far) (include/avr.h: safety, tightness,
+        miss). out: two contiguous fp32 tensors of one element per ray to write into. Nothing is read back: the call
+        may be captured in a graph."""
+        shape = ro.shape[:-1]
+        ro = ro.reshape(-1, 3).to(F32).contiguous()
+        rd = rd.reshape(-1, 3).to(F32).contiguous()
+        require_device(ro, rd, self.bits)
+        if out is None:
+            out = (torch.empty(ro.shape[0], device=ro.device, dtype=F32),
+                   torch.empty(ro.shape[0], device=ro.device, dtype=F32))
+        t_near, t_far = out
+        require_device(t_near, t_far)
+        if not all(t.dtype == F32 and t.numel() == ro.shape[0] for t in out):
+            raise ValueError(f"OccupancyGrid.ray_bounds: out must be two float32 tensors of {ro.shape[0]} elements")
+        call("avr_occ_ray_bounds", ctypes.byref(self.desc), ptr(ro), ptr(rd), ro.shape[0], float(near), float(far),
+             ptr(t_near), ptr(t_far), stream_of(ro))
+        return t_near.reshape(shape), t_far.reshape(shape)
+
     def live_fraction(self):
         """Share of the cells whose bit is set (a host read of the bits)."""
         words = self.bits.cpu().numpy().view(np.uint8)

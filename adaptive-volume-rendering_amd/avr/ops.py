@@ -150,16 +150,46 @@ def sample_coarse(near, far, n_rays, n_samples, device, noise=None, seed=0, offs
     return z
 
 
+def _ray_bounds(who, near, far, n_rays):
+    """Per-ray bounds as two contiguous fp32 device tensors of n_rays elements."""
+    near, far = _f32c(near.reshape(-1)), _f32c(far.reshape(-1))
+    if near.numel() != n_rays or far.numel() != n_rays:
+        raise _lib.AVRError(f"{who}: near / far have {near.numel()} / {far.numel()} entries for {n_rays} rays")
+    require_device(near, far)
+    return near, far
+
+
+def sample_coarse_bounds(near, far, n_samples, noise=None, seed=0, offset=0, ray_ids=None):
+    """sample_coarse with per-ray bounds near, far (R,) (avr_sample_coarse_bounds) -> z (R, n_samples); noise, seed,
+    offset and ray_ids as sample_coarse. Equal bounds give sample_coarse's bits."""
+    n_rays = near.numel()
+    near, far = _ray_bounds("sample_coarse_bounds", near, far, n_rays)
+    z = torch.empty(n_rays, n_samples, device=near.device, dtype=F32)
+    if noise is not None:
+        noise = _f32c(noise.reshape(n_rays, n_samples))
+        require_device(noise)
+    ray_ids = _ray_ids(ray_ids, n_rays)
+    call("avr_sample_coarse_bounds", ptr(near), ptr(far), n_rays, n_samples, ptr(noise), seed, offset, ptr(ray_ids),
+         ptr(z), stream_of(z))
+    return z
+
+
 def sample_fine(weights, z_coarse, near, far, n_importance, n_depth, depth_std, u=None, u2=None, noise_depth=None,
                 seed=0, offset=0, want_idx=False, want_fine=False, ray_ids=None):
     """sample_fine + sample_depth + clamp + sort (renderers.py:27-66, :252-258).
-    weights, z_coarse (R, Nc) -> z_sorted (R, Nc+Nf+Nd) [, idx (R,Nf) int32, z_fine (R,Nf)]."""
+    weights, z_coarse (R, Nc) -> z_sorted (R, Nc+Nf+Nd) [, idx (R,Nf) int32, z_fine (R,Nf)].
+    near, far: two floats, or two (R,) tensors of per-ray bounds (avr_sample_fine_bounds)."""
     R, Nc = z_coarse.shape
     weights = _f32c(weights.reshape(R, Nc))
     z_coarse = _f32c(z_coarse)
     dev = z_coarse.device
     if (u is None) != (u2 is None):
         raise _lib.AVRError("sample_fine: u and u2 must be given together")
+    per_ray = torch.is_tensor(near)
+    if per_ray != torch.is_tensor(far):
+        raise _lib.AVRError("sample_fine: near and far must be two floats or two (R,) tensors")
+    if per_ray:
+        near, far = _ray_bounds("sample_fine", near, far, R)
     if u is not None:
         u = _f32c(u.reshape(R, n_importance))
         u2 = _f32c(u2.reshape(R, n_importance))
@@ -169,6 +199,11 @@ def sample_fine(weights, z_coarse, near, far, n_importance, n_depth, depth_std, 
     z_sorted = torch.empty(R, Nc + n_importance + n_depth, device=dev, dtype=F32)
     idx = torch.empty(R, n_importance, device=dev, dtype=torch.int32) if want_idx else None
     z_fine = torch.empty(R, n_importance, device=dev, dtype=F32) if want_fine else None
+    if per_ray:
+        call("avr_sample_fine_bounds", ptr(weights), ptr(z_coarse), ptr(near), ptr(far), R, Nc, n_importance, n_depth,
+             float(depth_std), ptr(u), ptr(u2), ptr(noise_depth), seed, offset, ptr(ray_ids), ptr(z_sorted), ptr(idx),
+             ptr(z_fine), stream_of(z_coarse))
+        return z_sorted, idx, z_fine
     call("avr_sample_fine", ptr(weights), ptr(z_coarse), float(near), float(far), R, Nc, n_importance, n_depth,
          float(depth_std), ptr(u), ptr(u2), ptr(noise_depth), seed, offset, ptr(ray_ids), ptr(z_sorted), ptr(idx),
          ptr(z_fine),

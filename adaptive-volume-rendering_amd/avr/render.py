@@ -7,6 +7,7 @@ harness, utils.py:481-537, on the fused path; BASELINE configs 4 and 5).
     python -m avr.render --occupancy 128 [--occupancy-sigma 0.0]   # skip empty space (avr.occupancy); prints the live share
     python -m avr.render --occupancy 128 --occupancy-refine 4      # the grid built hierarchically: the field only under a live 32^3 grid
     python -m avr.render --occupancy 128 --occupancy-count device  # the same with the live count kept on the device
+    python -m avr.render --occupancy 128 --ray-bounds grid         # every ray samples the span of its own occupied cells
     python -m avr.render --t-stop 1e-3 --t-stop-count device [--occupancy 128]   # termination without host reads
 
 Renders `--frames` views on the reference's camera ring (radius, height 0.4)
@@ -92,6 +93,9 @@ def main(argv=None):
     ap.add_argument("--occupancy-probe", type=int, default=None, metavar="P",
                     help="with --occupancy-refine: judge every coarse cell at P^3 interior points (P = 1, 2 or 4; "
                          "default 1: its centre alone) at P^3 times the coarse stage's cost")
+    ap.add_argument("--ray-bounds", choices=("grid",), default=None,
+                    help="with --occupancy: every ray spreads its samples over the span of its own occupied cells "
+                         "instead of [near, far] (avr_occ_ray_bounds; a ray that misses them keeps [near, far])")
     ap.add_argument("--occupancy-count", choices=("host", "device"), default=None,
                     help="with --occupancy: where the live count of a gated pass is kept. host (default): read back "
                          "once per pass to size the launches; device: never read back, worst-case buffers (40 B per "
@@ -108,7 +112,7 @@ def main(argv=None):
     try:   # the counts as given (None: flag not given), so that a count given without its feature is refused too
         flag = lambda n: "--" + n.replace("_", "-")  # noqa: E731
         check_skip_modes("", args.t_stop, args.t_stop_count, args.occupancy, args.occupancy_count, idle=None,
-                         name=flag)
+                         name=flag, ray_bounds=args.ray_bounds)
         check_refine_modes("", args.occupancy, args.occupancy_refine, args.occupancy_probe, idle=None, name=flag)
     except ValueError as e:
         ap.error(str(e))
@@ -161,6 +165,7 @@ def main(argv=None):
             torch.cuda.synchronize()
             occupancy_build_ms = (time.perf_counter() - t_build) * 1e3
             rend.occupancy_count = occupancy_count
+            rend.ray_bounds = args.ray_bounds
     K = torch.tensor([INTRINSICS], device=device)
     H = W = args.res
     x_pix = get_opencv_pixel_coordinates(H, W).reshape(1, -1, 2).to(device)
@@ -217,6 +222,7 @@ def main(argv=None):
             # the live share: field samples evaluated over both passes' n_coarse + (n_coarse + n_fine) per ray
             line.update({"occupancy": args.occupancy, "occupancy_sigma": args.occupancy_sigma,
                          "occupancy_count": occupancy_count, "occupancy_refine": args.occupancy_refine,
+                         "ray_bounds": args.ray_bounds,
                          "occupancy_build_evals": rend.occupancy.build_evals,
                          "occupancy_build_ms": round(occupancy_build_ms, 3),
                          "occupancy_cells_set": round(rend.occupancy.live_fraction(), 4),

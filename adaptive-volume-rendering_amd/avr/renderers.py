@@ -115,13 +115,19 @@ def volume_integral_packed(z_vals, field, white_back=True, infinity=1.8):
 _ANY = object()
 
 
-def check_skip_modes(who, t_stop, t_stop_count, occupancy, occupancy_count, idle=_ANY, capture=False, name=str):
+def check_skip_modes(who, t_stop, t_stop_count, occupancy, occupancy_count, idle=_ANY, capture=False, name=str,
+                     ray_bounds=None):
     """What combines of early termination (t_stop, t_stop_count) and occupancy gating (occupancy, occupancy_count),
     stated once; ValueError otherwise. A count is 'host' or 'device'; occupancy with t_stop needs t_stop_count =
     'device'; with `idle` given, a count may hold nothing but `idle` while its feature is None (render_orbit: 'host',
     its default; the CLI: None, a flag not given; left out: the renderer's attributes always hold a mode); with
-    `capture`, the call is to be recorded in a graph, which no host-count mode can be. `who` opens the message and
-    `name` spells the four names in the caller's vocabulary (the CLI: its flags)."""
+    `capture`, the call is to be recorded in a graph, which no host-count mode can be. ray_bounds is None or 'grid'
+    (per-ray sampling bounds from the occupancy grid), and 'grid' needs occupancy. `who` opens the message and
+    `name` spells the names in the caller's vocabulary (the CLI: its flags)."""
+    if ray_bounds not in (None, "grid"):
+        raise ValueError(f"{who}{name('ray_bounds')} must be None or 'grid', got {ray_bounds!r}")
+    if ray_bounds is not None and occupancy is None:
+        raise ValueError(f"{who}{name('ray_bounds')} needs {name('occupancy')} (the bounds come from its grid)")
     for feature, count, f, c in ((t_stop, t_stop_count, "t_stop", "t_stop_count"),
                                  (occupancy, occupancy_count, "occupancy", "occupancy_count")):
         if count not in ("host", "device", idle):
@@ -179,6 +185,22 @@ class VolumeRenderer(nn.Module):
         # fine samples that reached the field summed over chunks and scenes; captured launches write it.
         self.t_stop_count = "host"
         self.last_fine_counts = None
+        # Per-ray sampling bounds (not in the reference): None = every ray spreads its samples over [near, far];
+        # "grid" = over the span of its own occupied cells (OccupancyGrid.ray_bounds; a ray that misses them keeps
+        # [near, far]), so the same sample counts fall more densely where gating evaluates them. Needs `occupancy`;
+        # inference on the fused path only. last_ray_bounds: the (t_near, t_far) (SB, R) of the last such call.
+        self.ray_bounds = None
+        self.last_ray_bounds = None
+
+    @property
+    def ray_bounds(self):
+        return self._ray_bounds
+
+    @ray_bounds.setter
+    def ray_bounds(self, mode):
+        if mode not in (None, "grid"):   # (that 'grid' needs `occupancy` is checked per call: either may be set first)
+            raise ValueError(f"VolumeRenderer: ray_bounds must be None or 'grid', got {mode!r}")
+        self._ray_bounds = mode
 
     @property
     def occupancy_count(self):
@@ -206,7 +228,8 @@ class VolumeRenderer(nn.Module):
         if torch.is_grad_enabled():
             raise ValueError("VolumeRenderer.occupancy is inference only: call under torch.no_grad()")
         check_skip_modes("VolumeRenderer: ", self.t_stop, self.t_stop_count, occ, self.occupancy_count,
-                         capture=dev.type == "cuda" and torch.cuda.is_current_stream_capturing())
+                         capture=dev.type == "cuda" and torch.cuda.is_current_stream_capturing(),
+                         ray_bounds=self.ray_bounds)
         if len(grids) != SB:
             raise ValueError(f"VolumeRenderer.occupancy holds {len(grids)} grid(s) for {SB} scene(s)")
         if self.n_coarse + self.n_fine > _lib.OCC_MAX_SAMPLES:
@@ -317,6 +340,9 @@ class VolumeRenderer(nn.Module):
         nf = self.n_fine - self.n_fine_depth
         Nc, Nt = self.n_coarse, self.n_coarse + self.n_fine
         fuse = hasattr(radiance_field, "can_fuse") and radiance_field.can_fuse(x_pix)
+        if self.ray_bounds is not None and self.occupancy is None:   # never a quiet render without bounds
+            check_skip_modes("VolumeRenderer: ", self.t_stop, self.t_stop_count, None, self.occupancy_count,
+                             ray_bounds=self.ray_bounds)
         grids = None if self.occupancy is None else self._occupancy_grids(SB, radiance_field, fuse, dev)
         stop_on_device = self.t_stop is not None and self.t_stop_count == "device" and not torch.is_grad_enabled()
         if stop_on_device:
@@ -336,6 +362,19 @@ class VolumeRenderer(nn.Module):
         ro, rd, zc, depth_row, c2w_info = ops.rays_sample_coarse(
             x_pix, intrinsics, cam2world, near, far, Nc, noise=None if draws is None else draws["coarse"], seed=seed,
             offset=off, ray_ids=ids, want_depth_row=fast_depth)
+
+        near_r = far_r = None
+        if self.ray_bounds is not None:
+            # each scene's rays against its own grid, then the coarse z over each ray's own span (the launch above
+            # gave the rays and their depth rows; its z, over [near, far], is replaced). The bounds depend on the ray
+            # alone and the draws are keyed as before, so a shard's rows are the frame's.
+            near_r = torch.empty(SB * R, device=dev, dtype=torch.float32)
+            far_r = torch.empty_like(near_r)
+            for b in range(SB):
+                grids[b].ray_bounds(ro[b], rd[b], near, far, out=(near_r[b * R:(b + 1) * R], far_r[b * R:(b + 1) * R]))
+            zc = ops.sample_coarse_bounds(near_r, far_r, Nc, noise=None if draws is None else draws["coarse"],
+                                          seed=seed, offset=off, ray_ids=ids)
+            self.last_ray_bounds = (near_r.reshape(SB, R), far_r.reshape(SB, R))
 
         self.last_path = "fused" if fuse else "module"
         live = []
@@ -367,7 +406,8 @@ class VolumeRenderer(nn.Module):
         fc = field(zc, True)
         rgb_c, dist_c, w_c = ops.composite(zc, fc, self.white_back)
         z_sorted, _, _ = ops.sample_fine(
-            w_c.detach(), zc, near, far, nf, self.n_fine_depth, self.depth_std,
+            w_c.detach(), zc, near if near_r is None else near_r, far if far_r is None else far_r, nf,
+            self.n_fine_depth, self.depth_std,
             u=None if draws is None else draws["u"], u2=None if draws is None else draws["u2"],
             noise_depth=None if draws is None else draws["depth"], seed=seed, offset=off, ray_ids=ids)
         if stop_on_device:

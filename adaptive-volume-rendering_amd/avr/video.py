@@ -117,7 +117,8 @@ def check_refine_modes(who, occupancy, refine, probe, idle=None, name=str):
 
 def render_orbit(renderer, radiance_field, intrinsics, num_frames, radius, height, width=None, fine=True,
                  device=None, t_stop=None, on_frame=None, occupancy=None, occupancy_sigma=0.0, occupancy_box=1.0,
-                 occupancy_count="host", t_stop_count="host", occupancy_refine=None, occupancy_probe=1):
+                 occupancy_count="host", t_stop_count="host", occupancy_refine=None, occupancy_probe=1,
+                 ray_bounds=None):
     """Render num_frames full frames around the orbit with `renderer`
     (e.g. avr.renderers.VolumeRenderer) and a ready radiance field. One
     renderer call per frame (all H * W rays at once), no_grad. Returns
@@ -134,9 +135,12 @@ def render_orbit(renderer, radiance_field, intrinsics, num_frames, radius, heigh
     summed on the device and read once after the last frame.
     occupancy_refine = F (2, 4 or 8), occupancy_probe = P (1, 2 or 4): the grid is built hierarchically
     (from_field(refine=F, coarse_probe=P): the field only under the live cells of a (RES / F)^3 grid); both need
-    occupancy. stats then carry occupancy_build_evals and occupancy_build_ms."""
+    occupancy. stats then carry occupancy_build_evals and occupancy_build_ms.
+    ray_bounds = None | "grid" (renderer.ray_bounds for these frames; "grid" needs occupancy): every ray samples the
+    span of its own occupied cells; stats then carry ray_bounds."""
     from .renderers import check_skip_modes
-    check_skip_modes("render_orbit: ", t_stop, t_stop_count, occupancy, occupancy_count, idle="host")
+    check_skip_modes("render_orbit: ", t_stop, t_stop_count, occupancy, occupancy_count, idle="host",
+                     ray_bounds=ray_bounds)
     check_refine_modes("render_orbit: ", occupancy, occupancy_refine, occupancy_probe, idle=1)
     width = width or height
     device = device or intrinsics.device
@@ -162,6 +166,8 @@ def render_orbit(renderer, radiance_field, intrinsics, num_frames, radius, heigh
         modes["t_stop_count"] = t_stop_count
     if grid is not None:
         modes.update(occupancy=grid, occupancy_count=occupancy_count)
+    if ray_bounds is not None:
+        modes["ray_bounds"] = ray_bounds
     frames = []
     counts = FrameCounts(t_stop is not None and t_stop_count == "device",
                          grid is not None and occupancy_count == "device")
@@ -187,6 +193,7 @@ def render_orbit(renderer, radiance_field, intrinsics, num_frames, radius, heigh
         per_ray = 2 * renderer.n_coarse + renderer.n_fine    # the coarse pass, then coarse + fine positions again
         stats["live_share"] = live_samples / max(num_frames * n * per_ray, 1)
         stats["occupancy_count"] = occupancy_count
+        stats["ray_bounds"] = ray_bounds
         stats.update(occupancy_refine=occupancy_refine, occupancy_build_evals=grid.build_evals,
                      occupancy_build_ms=build_ms)
         print(f"occupancy {occupancy}^3: {stats['live_share']:.4f} of the field samples were live")
@@ -194,7 +201,7 @@ def render_orbit(renderer, radiance_field, intrinsics, num_frames, radius, heigh
 
 
 def generate_video(model_input, num_frames, radius, net, model, fine=True, occupancy=None, occupancy_count="host",
-                   t_stop_count="host", occupancy_refine=None, occupancy_probe=1):
+                   t_stop_count="host", occupancy_refine=None, occupancy_probe=1, ray_bounds=None):
     """utils.py:481-537 with the same arguments: encode the first source view
     of model_input into `net`, then render the orbit through `model`
     (a RadFieldAndRenderer). A net whose latent was set with encode_latent()
@@ -202,7 +209,8 @@ def generate_video(model_input, num_frames, radius, net, model, fine=True, occup
     occupancy = RES, occupancy_count = "host" | "device": render_orbit's empty-space skipping (not in the
     reference; off by default). t_stop_count = "host" | "device": where render_orbit keeps the counts of the
     renderer's early termination (model.renderer.t_stop; "device" needs it set). occupancy_refine = F,
-    occupancy_probe = P: render_orbit's hierarchical grid build."""
+    occupancy_probe = P: render_orbit's hierarchical grid build. ray_bounds = None | "grid": render_orbit's per-ray
+    sampling bounds from the grid."""
     intrinsics = model_input["intrinsics"][0:1, 0, ...]
     if "images" in model_input and net.encoder.latent.shape[-1] <= 1:   # no latent yet
         gt = model_input["images"]
@@ -216,7 +224,8 @@ def generate_video(model_input, num_frames, radius, net, model, fine=True, occup
     frames, stats = render_orbit(model.renderer, net, intrinsics, num_frames, radius, sl, fine=fine,
                                  t_stop=t_stop, occupancy=occupancy,
                                  occupancy_count=occupancy_count, t_stop_count=t_stop_count,
-                                 occupancy_refine=occupancy_refine, occupancy_probe=occupancy_probe)
+                                 occupancy_refine=occupancy_refine, occupancy_probe=occupancy_probe,
+                                 ray_bounds=ray_bounds)
     print(f"it takes {stats['seconds']} seconds to render a video")
     return frames
 

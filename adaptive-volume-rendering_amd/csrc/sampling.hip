@@ -101,6 +101,55 @@ __global__ void __launch_bounds__(256) sample_coarse_rays_kernel(const float* __
   z[i] = coarse_z<false>(nr, span, s, n, u, 0.f);
 }
 
+// sample_coarse_kernel with per-ray bounds near_r, far_r (n_rays): the same 4-sample quads, draws, keying by ray_ids
+// and stores; a sample is coarse_z's four operations on the ray's own near and span, which are the operations
+// sample_coarse_kernel's table splits in two, so equal bounds give equal bits.
+template <bool POW2>
+__global__ void __launch_bounds__(256) sample_coarse_bounds_kernel(const float* __restrict__ near_r,
+                                                                   const float* __restrict__ far_r, int64_t n_rays,
+                                                                   int n, const float* __restrict__ noise,
+                                                                   uint64_t seed, uint64_t offset,
+                                                                   const int64_t* __restrict__ ray_ids,
+                                                                   float* __restrict__ z) {
+  const int nq = (n + 3) >> 2;
+  const float inv_n = 1.0f / (float)n;
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int64_t total = n_rays * nq;
+  if (i >= total) return;
+  int64_t r;
+  int q;
+  if (total < (1ll << 32)) {
+    const unsigned ui = (unsigned)i, ur = ui / (unsigned)nq;
+    r = ur;
+    q = (int)(ui - ur * (unsigned)nq);
+  } else {
+    r = i / nq;
+    q = (int)(i - r * nq);
+  }
+  const float nr = near_r[r];
+  const float span = fsub(far_r[r], nr);
+  float u[4];
+  if (noise) {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) u[k] = 4 * q + k < n ? noise[r * n + 4 * q + k] : 0.f;
+  } else {
+    const uint64_t key = offset + (uint64_t)(ray_ids ? ray_ids[r] : r);
+    const float4 v = philox_uniform4(seed, key, (uint32_t)q, kStreamCoarse);
+    u[0] = v.x; u[1] = v.y; u[2] = v.z; u[3] = v.w;
+  }
+  float o[4];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) o[k] = coarse_z<POW2>(nr, span, 4 * q + k, n, u[k], inv_n);
+  float* zr = z + r * n + 4 * q;
+  if ((n & 3) == 0) {
+    *reinterpret_cast<floatx4*>(zr) = floatx4{o[0], o[1], o[2], o[3]};
+  } else {
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+      if (4 * q + k < n) zr[k] = o[k];
+  }
+}
+
 // get_world_rays (utils.py:315-336) + sample_coarse (renderers.py:4-24) in one
 // launch, plus each ray's depth row for the composite epilogue. A workgroup
 // owns kRaysPerBlock (64) consecutive rays: wave 0 builds ro, rd with one lane
@@ -388,174 +437,24 @@ __global__ void __launch_bounds__(256) sample_fine_kernel(
   const int lane = threadIdx.x & 63, wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // wid, ray: scalars
   const int64_t ray = (int64_t)blockIdx.x * kFineWaves + wid;
   if (ray >= n_rays) return;  // wave-uniform
-  const int Nc = NC ? NC : Nc_, Nf = NC ? NF : Nf_, Nd = NC ? ND : Nd_;
-  const int Ntot = Nc + Nf + Nd;
-  float* cdf = lds + (size_t)wid * fine_wave_floats(Nc, sort_n, Ntot);   // [0 .. Nc]
-  float* scratch = cdf + Nc + 1;
-  float* sbuf = scratch + 64;   // lists: coarse [0, Nc) | fine [Nc, Nc+Nf) | depth [Nc+Nf, Ntot)
-  float* obuf = sbuf + sort_n;
-  const float span = fsub(far_, near_);
-  const uint64_t key = offset + (uint64_t)(ray_ids ? ray_ids[ray] : ray);   // Philox counter of this ray
-  const float inv_nc = 1.0f / (float)Nc;
+#include "sample_fine_body.h"
+}
 
-  // 1) + 2)
-  const float* w = weights + ray * Nc;
-  const float* zc = z_coarse + ray * Nc;
-  bool coarse_sorted = true;
-  float wv[kMaxK], zv[kMaxK];
-#pragma unroll
-  for (int m = 0; m < kMaxK; ++m) {
-    const int k = lane + 64 * m;
-    wv[m] = k < Nc ? w[k] : 0.f;
-    zv[m] = k < Nc ? zc[k] : 0.f;
-  }
-  // the in-kernel (u, u2) draw of this lane's fine sample does not depend on
-  // the weights: it runs while their loads are in flight (one sample per lane)
-  float4 draw = {0.f, 0.f, 0.f, 0.f};
-  if (!u_in && Nf <= 64 && lane < Nf) draw = philox_uniform4(seed, key, (uint32_t)lane, kStreamFine);
-  float xr[kMaxK];
-#pragma unroll
-  for (int m = 0; m < kMaxK; ++m) {
-    const int k = lane + 64 * m;
-    xr[m] = 0.f;
-    if (k < Nc) {
-      xr[m] = fadd(wv[m], 1e-5f);
-      cdf[1 + k] = xr[m];
-      sbuf[k] = zv[m];
-    }
-  }
-  float s;
-  if ((Nc & 63) == 0) {
-    s = cascade_sum_regs(xr, Nc >> 6, lane);
-    wave_sync();
-  } else {
-    wave_sync();
-    s = cascade_sum_wave(cdf + 1, Nc, lane, scratch);
-  }
-  for (int k = lane; k + 1 < Nc; k += 64) coarse_sorted &= sbuf[k] <= sbuf[k + 1];
-  coarse_sorted = __all(coarse_sorted);
-  {
-    const int K = (Nc + 63) >> 6, k0 = K * lane;
-    float pv[kMaxK];
-    double part = 0.0;
-#pragma unroll
-    for (int k = 0; k < kMaxK; ++k) {
-      pv[k] = (k < K && k0 + k < Nc) ? fdiv(cdf[1 + k0 + k], s) : 0.f;
-      part += (double)pv[k];
-    }
-    double run = wave_excl_sum_dpp(part);
-    wave_sync();   // every pdf read before any cdf write
-#pragma unroll
-    for (int k = 0; k < kMaxK; ++k)
-      if (k < K && k0 + k < Nc) {
-        run += (double)pv[k];
-        cdf[1 + k0 + k] = (float)run;
-      }
-    if (lane == 0) cdf[0] = 0.f;
-  }
-  wave_sync();
-
-  // 3) importance samples
-  float zf_mine = FLT_MAX;
-  for (int f = lane; f < Nf; f += 64) {
-    float u, u2;
-    if (u_in) {
-      u = u_in[ray * Nf + f];
-      u2 = u2_in[ray * Nf + f];
-    } else {
-      const float4 v = Nf <= 64 ? draw : philox_uniform4(seed, key, (uint32_t)f, kStreamFine);
-      u = v.x;
-      u2 = v.y;
-    }
-    const int cnt = count_below<false>(cdf, Nc + 1, u);   // #{cdf <= u}
-    const int idx = cnt > 0 ? cnt - 1 : 0;
-    const float steps = div_count<POW2>(fadd((float)idx, u2), (float)Nc, inv_nc);
-    const float zf = fadd(near_, fmul(span, steps));
-    if (idx_out) idx_out[ray * Nf + f] = idx;
-    if (z_fine_out) z_fine_out[ray * Nf + f] = zf;
-    sbuf[Nc + f] = zf;
-    zf_mine = zf;
-  }
-  // 4) depth samples: clamp(randn * std, near, far)  (quirk Q6)
-  float zd_mine = FLT_MAX;
-  for (int d = lane; d < Nd; d += 64) {
-    const float n = nd_in ? nd_in[ray * Nd + d] : philox_normal(seed, key, d, kStreamDepth);
-    zd_mine = fminf(fmaxf(fmul(n, depth_std), near_), far_);
-    sbuf[Nc + Nf + d] = zd_mine;
-  }
-  wave_sync();
-
-  // 5) sort
-  float* out = z_sorted + ray * Ntot;
-  if (coarse_sorted && Nf <= 64 && Nd == 0) {
-    // two lists: the fine values take slots lane + #{A <= bf} (increasing in
-    // lane); the coarse values fill the other slots in order. A slot's list
-    // index = the number of fine slots before it (ballot + mbcnt) or the rest.
-    const float* A = sbuf;
-    float* B = sbuf + Nc;
-    int* marks = reinterpret_cast<int*>(obuf);
-    for (int k = lane; k < Ntot; k += 64) marks[k] = 0;
-    const float bf = wave_sort64(zf_mine, lane);
-    wave_sync();   // the unsorted fine list is read by nobody past this point
-    if (lane < Nf) {
-      B[lane] = bf;
-      const float t = (bf - near_) * ((float)Nc * __builtin_amdgcn_rcpf(span));   // a guess: verified below
-      const int g = t > 0.f ? (t < (float)Nc ? (int)t : Nc) : 0;
-      marks[lane + count_below_near<false>(A, Nc, bf, g)] = 1;
-    }
-    wave_sync();
-    int base = 0;
-    for (int s0 = 0; s0 < Ntot; s0 += 64) {
-      const int k = s0 + lane;
-      const bool fine = k < Ntot && marks[k] != 0;
-      const uint64_t mask = __ballot(fine);
-      const int before = base + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32),
-                                                               __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0u));
-      if (k < Ntot) out[k] = sbuf[fine ? Nc + before : k - before];   // B[before] or A[k - before]: one read
-      base += __popcll(mask);
-    }
-    return;
-  }
-  if (coarse_sorted && Nf <= 64 && Nd <= 64) {
-    const float* A = sbuf;
-    float* B = sbuf + Nc;
-    float* D = sbuf + Nc + Nf;
-    const float bf = wave_sort64(zf_mine, lane);
-    const float bd = Nd > 0 ? wave_sort64(zd_mine, lane) : FLT_MAX;
-    wave_sync();   // the unsorted lists are read by nobody past this point
-    if (lane < Nf) B[lane] = bf;
-    if (lane < Nd) D[lane] = bd;
-    wave_sync();
-    for (int k = lane; k < Nc; k += 64) {
-      const float x = A[k];
-      obuf[k + count_below<true>(B, Nf, x) + count_below<true>(D, Nd, x)] = x;
-    }
-    if (lane < Nf) {
-      // stratified coarse lists put #{A <= bf} within a step of bf's bin
-      const float t = (bf - near_) * ((float)Nc * __builtin_amdgcn_rcpf(span));   // a guess: verified below
-      const int g = t > 0.f ? (t < (float)Nc ? (int)t : Nc) : 0;
-      obuf[lane + count_below_near<false>(A, Nc, bf, g) + count_below<true>(D, Nd, bf)] = bf;
-    }
-    if (lane < Nd) obuf[lane + count_below<false>(A, Nc, bd) + count_below<false>(B, Nf, bd)] = bd;
-    wave_sync();
-    for (int k = lane; k < Ntot; k += 64) out[k] = obuf[k];
-    return;
-  }
-  for (int k = Ntot + lane; k < sort_n; k += 64) sbuf[k] = FLT_MAX;
-  wave_sync();
-  for (int size = 2; size <= sort_n; size <<= 1) {
-    for (int stride = size >> 1; stride > 0; stride >>= 1) {
-      for (int t = lane; t < (sort_n >> 1); t += 64) {
-        const int i = 2 * t - (t & (stride - 1));
-        const int j = i + stride;
-        const float a = sbuf[i], b = sbuf[j];
-        const bool up = ((i & size) == 0);
-        if ((a > b) == up) { sbuf[i] = b; sbuf[j] = a; }
-      }
-      wave_sync();
-    }
-  }
-  for (int k = lane; k < Ntot; k += 64) out[k] = sbuf[k];
+// sample_fine with per-ray bounds near_r, far_r (n_rays): avr_occ_ray_bounds' span of each ray. Where every element
+// equals the scalars, every operation is sample_fine_kernel's on the same operands.
+template <bool POW2, int NC = 0, int NF = 0, int ND = 0>
+__global__ void __launch_bounds__(256) sample_fine_bounds_kernel(
+    const float* __restrict__ weights, const float* __restrict__ z_coarse, const float* __restrict__ near_r,
+    const float* __restrict__ far_r, int64_t n_rays, int Nc_, int Nf_, int Nd_, float depth_std,
+    const float* __restrict__ u_in, const float* __restrict__ u2_in, const float* __restrict__ nd_in, uint64_t seed,
+    uint64_t offset, const int64_t* __restrict__ ray_ids, int sort_n, float* __restrict__ z_sorted,
+    int32_t* __restrict__ idx_out, float* __restrict__ z_fine_out) {
+  extern __shared__ float lds[];
+  const int lane = threadIdx.x & 63, wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int64_t ray = (int64_t)blockIdx.x * kFineWaves + wid;
+  if (ray >= n_rays) return;  // wave-uniform
+  const float near_ = near_r[ray], far_ = far_r[ray];
+#include "sample_fine_body.h"
 }
 
 // AdaptiveVolumeRenderer's band in training (renderers.py:490-496 and the band points, :497-508): per ray the
@@ -665,30 +564,80 @@ extern "C" int avr_sample_coarse_rays(const float* near_, const float* far_, int
   return check_launch("sample_coarse_rays_kernel");
 }
 
+// The argument checks and the launch shape avr_sample_fine and avr_sample_fine_bounds share.
+static int fine_args(const char* who, const void* weights, const void* z_coarse, const void* z_sorted, int64_t n_rays,
+                     int n_coarse, int n_importance, int n_depth, const float* u, const float* u2,
+                     const float* noise_depth, int* sort_n, unsigned* grid, size_t* shm) {
+  AVR_REQUIRE(n_rays >= 0, "%s: negative n_rays", who);
+  AVR_REQUIRE(n_rays == 0 || (weights && z_coarse && z_sorted), "%s: null pointer", who);
+  AVR_REQUIRE(n_coarse > 0 && n_coarse <= kMaxCoarse, "%s: n_coarse must be in [1, %d]", who, kMaxCoarse);
+  AVR_REQUIRE(n_importance >= 0 && n_depth >= 0, "%s: negative sample count", who);
+  const int ntot = n_coarse + n_importance + n_depth;
+  AVR_REQUIRE(ntot <= kMaxSort, "%s: total samples %d > %d", who, ntot, kMaxSort);
+  const bool explicit_noise = (u != nullptr);
+  AVR_REQUIRE(explicit_noise == (u2 != nullptr) && (n_depth == 0 || explicit_noise == (noise_depth != nullptr)),
+              "%s: u, u2, noise_depth must be all given or all NULL", who);
+  *sort_n = 2;
+  while (*sort_n < ntot) *sort_n <<= 1;
+  AVR_REQUIRE((n_rays + kFineWaves - 1) / kFineWaves < (1ll << 31), "%s: too many rays", who);
+  *grid = (unsigned)((n_rays + kFineWaves - 1) / kFineWaves);
+  *shm = (size_t)kFineWaves * fine_wave_floats(n_coarse, *sort_n, ntot) * sizeof(float);
+  return AVR_OK;
+}
+
 extern "C" int avr_sample_fine(const float* weights, const float* z_coarse, float near_, float far_, int64_t n_rays,
                                int n_coarse, int n_importance, int n_depth, float depth_std, const float* u,
                                const float* u2, const float* noise_depth, uint64_t seed, uint64_t offset,
                                const int64_t* ray_ids, float* z_sorted, int32_t* idx, float* z_fine, void* stream) {
-  AVR_REQUIRE(n_rays >= 0, "avr_sample_fine: negative n_rays");
-  AVR_REQUIRE(n_rays == 0 || (weights && z_coarse && z_sorted), "avr_sample_fine: null pointer");
-  AVR_REQUIRE(n_coarse > 0 && n_coarse <= kMaxCoarse, "avr_sample_fine: n_coarse must be in [1, %d]", kMaxCoarse);
-  AVR_REQUIRE(n_importance >= 0 && n_depth >= 0, "avr_sample_fine: negative sample count");
-  const int ntot = n_coarse + n_importance + n_depth;
-  AVR_REQUIRE(ntot <= kMaxSort, "avr_sample_fine: total samples %d > %d", ntot, kMaxSort);
-  const bool explicit_noise = (u != nullptr);
-  AVR_REQUIRE(explicit_noise == (u2 != nullptr) && (n_depth == 0 || explicit_noise == (noise_depth != nullptr)),
-              "avr_sample_fine: u, u2, noise_depth must be all given or all NULL");
+  int sort_n;
+  unsigned grid;
+  size_t shm;
+  const int rc = fine_args("avr_sample_fine", weights, z_coarse, z_sorted, n_rays, n_coarse, n_importance, n_depth, u,
+                           u2, noise_depth, &sort_n, &grid, &shm);
+  if (rc) return rc;
   if (n_rays == 0) return AVR_OK;
-  int sort_n = 2;
-  while (sort_n < ntot) sort_n <<= 1;
-  const unsigned grid = (unsigned)((n_rays + kFineWaves - 1) / kFineWaves);
-  const size_t shm = (size_t)kFineWaves * fine_wave_floats(n_coarse, sort_n, ntot) * sizeof(float);
   auto* kern = (n_coarse & (n_coarse - 1)) == 0 ? sample_fine_kernel<true> : sample_fine_kernel<false>;
   if (n_coarse == 128 && n_importance == 64 && n_depth == 0) kern = sample_fine_kernel<true, 128, 64, 0>;
   kern<<<grid, 64 * kFineWaves, shm, as_stream(stream)>>>(
       weights, z_coarse, near_, far_, n_rays, n_coarse, n_importance, n_depth, depth_std, u, u2, noise_depth, seed,
       offset, ray_ids, sort_n, z_sorted, idx, z_fine);
   return check_launch("sample_fine_kernel");
+}
+
+extern "C" int avr_sample_coarse_bounds(const float* near_r, const float* far_r, int64_t n_rays, int n_samples,
+                                        const float* noise, uint64_t seed, uint64_t offset, const int64_t* ray_ids,
+                                        float* z, void* stream) {
+  AVR_REQUIRE(n_rays >= 0 && n_samples > 0, "avr_sample_coarse_bounds: bad sizes");
+  if (n_rays == 0) return AVR_OK;
+  AVR_REQUIRE(near_r && far_r && z, "avr_sample_coarse_bounds: null pointer");
+  const int64_t blocks = (n_rays * ((n_samples + 3) / 4) + 255) / 256;
+  AVR_REQUIRE(blocks < (1ll << 31), "avr_sample_coarse_bounds: too many rays");
+  auto* kern = (n_samples & (n_samples - 1)) == 0 ? sample_coarse_bounds_kernel<true>
+                                                  : sample_coarse_bounds_kernel<false>;
+  kern<<<(unsigned)blocks, 256, 0, as_stream(stream)>>>(near_r, far_r, n_rays, n_samples, noise, seed, offset, ray_ids,
+                                                       z);
+  return check_launch("sample_coarse_bounds_kernel");
+}
+
+extern "C" int avr_sample_fine_bounds(const float* weights, const float* z_coarse, const float* near_r,
+                                      const float* far_r, int64_t n_rays, int n_coarse, int n_importance, int n_depth,
+                                      float depth_std, const float* u, const float* u2, const float* noise_depth,
+                                      uint64_t seed, uint64_t offset, const int64_t* ray_ids, float* z_sorted,
+                                      int32_t* idx, float* z_fine, void* stream) {
+  int sort_n;
+  unsigned grid;
+  size_t shm;
+  const int rc = fine_args("avr_sample_fine_bounds", weights, z_coarse, z_sorted, n_rays, n_coarse, n_importance,
+                           n_depth, u, u2, noise_depth, &sort_n, &grid, &shm);
+  if (rc) return rc;
+  AVR_REQUIRE(n_rays == 0 || (near_r && far_r), "avr_sample_fine_bounds: null bounds");
+  if (n_rays == 0) return AVR_OK;
+  auto* kern = (n_coarse & (n_coarse - 1)) == 0 ? sample_fine_bounds_kernel<true> : sample_fine_bounds_kernel<false>;
+  if (n_coarse == 128 && n_importance == 64 && n_depth == 0) kern = sample_fine_bounds_kernel<true, 128, 64, 0>;
+  kern<<<grid, 64 * kFineWaves, shm, as_stream(stream)>>>(
+      weights, z_coarse, near_r, far_r, n_rays, n_coarse, n_importance, n_depth, depth_std, u, u2, noise_depth, seed,
+      offset, ray_ids, sort_n, z_sorted, idx, z_fine);
+  return check_launch("sample_fine_bounds_kernel");
 }
 
 extern "C" int avr_band_fwd(int64_t n_rays, int n_samples, const float* world, const float* ro, const float* rd,

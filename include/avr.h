@@ -859,6 +859,41 @@ int avr_march_composite_masked(const float* z, const float* field_c, const uint6
                                int chunk, float infinity, float t_stop, void* state, int64_t* evaluated,
                                int accumulate, void* stream);
 
+/* ------------------------------------------ occupancy grid: per-ray bounds
+ * Additions within ABI 18 (no version change; DESIGN.md "Occupancy grid: per-ray sampling bounds"): where along
+ * [near_, far_] a ray's occupied cells begin and end, and the two sampling entries with per-ray bounds that place the
+ * renderer's samples there. "Live" below is avr_occ_classify's test: the fp32 point fadd(ro, fmul(rd, z)), the fp32
+ * cell coordinates, a non-finite coordinate live, a point outside the box dead.
+ *   avr_occ_ray_bounds: ro, rd (n_rays, 3) -> t_near, t_far (n_rays), near_ <= t_near[r] <= t_far[r] <= far_.
+ *     (S) Safety: every fp32 z in [near_, far_] that is live for ray r has t_near[r] <= z <= t_far[r]: no sample that
+ *       gating would have evaluated falls outside the bounds. A ray with a non-finite ro or rd component gets exactly
+ *       (near_, far_).
+ *     (T) Tightness: with [a, b] the hull, in exact arithmetic, of the ray's intersections with the occupied cells
+ *       clipped to [near_, far_], and slack = sqrt(3) * max_a(cell edge_a) / |rd|: a ray that crosses some occupied
+ *       cell shrunk by 1/8 of a cell edge on every side (a clear hit) has t_near >= a - slack, t_far <= b + slack.
+ *     (M) Miss: a ray that misses every occupied cell grown by 1/8 of a cell edge on every side (a clear miss) gets
+ *       exactly (near_, far_): gating evaluates none of its samples wherever they lie, and its sampling -- its
+ *       background pixel -- stays as it is without bounds, bit for bit.
+ *     A ray that is neither may get either answer; (S) and the range hold for it. An interval that is empty or
+ *     inverted after the clamp to [near_, far_] is reported as a miss. One ray per lane, no atomics: two launches give
+ *     the same bits.
+ *   avr_sample_coarse_bounds: avr_sample_coarse with near_r, far_r (n_rays) in place of the two scalars; noise,
+ *     seed, offset and ray_ids as there (the same Philox keying).
+ *   avr_sample_fine_bounds: avr_sample_fine with near_r, far_r (n_rays) in place of the two scalars: ray r's
+ *     importance samples are scaled to, and its depth samples clamped to (quirk Q6), its own [near_r[r], far_r[r]].
+ *   Where every element of near_r / far_r equals the scalars, both give their scalar counterpart's outputs bit for bit.
+ * Checked before any launch (AVR_E_INVALID): null pointers, a grid avr_occ_classify refuses, negative n_rays,
+ * !(near_ < far_), and what avr_sample_coarse / avr_sample_fine check. n_rays == 0 returns AVR_OK with no launch.  */
+int avr_occ_ray_bounds(const avr_occ_grid* grid, const float* ro, const float* rd, int64_t n_rays, float near_,
+                       float far_, float* t_near, float* t_far, void* stream);
+int avr_sample_coarse_bounds(const float* near_r, const float* far_r, int64_t n_rays, int n_samples,
+                             const float* noise, uint64_t seed, uint64_t offset, const int64_t* ray_ids, float* z,
+                             void* stream);
+int avr_sample_fine_bounds(const float* weights, const float* z_coarse, const float* near_r, const float* far_r,
+                           int64_t n_rays, int n_coarse, int n_importance, int n_depth, float depth_std,
+                           const float* u, const float* u2, const float* noise_depth, uint64_t seed, uint64_t offset,
+                           const int64_t* ray_ids, float* z_sorted, int32_t* idx, float* z_fine, void* stream);
+
 /* ------------------------------------------------------------ measurement
  * Streaming device copy dst[0, n_bytes) = src[0, n_bytes) (16-B aligned,
  * n_bytes a multiple of 16): the achievable-HBM yardstick bench.py reports
