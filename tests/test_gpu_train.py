@@ -170,6 +170,23 @@ def test_field_train_ragged_and_empty():
     assert out.shape == (1, 0, 4)
 
 
+@pytest.mark.parametrize("d_hidden", [128, 512])
+def test_field_train_grads_with_row_outliers(d_hidden):
+    """Rows of unequal weight: the loss weights of three rows scaled by 2^12 and of three others by 2^-12 (one of
+    each in the two-row last workgroup of M = 130), so the layer maxima avr_weight_grads scales by come from a few
+    rows while the others sit 24 binary orders below them. Held to float64 as every case above."""
+    net = _net(d_hidden, 3, 64, (8, 8), combine_layer=2)
+    xyz, vd, w = _points(1, 130, seed=17)
+    w[0, [5, 64, 129]] *= 2.0 ** 12
+    w[0, [6, 70, 128]] *= 2.0 ** -12
+    _, g_h, _ = _grads(net, xyz, vd, w, True, hip=True)
+    _, g_t, _ = _grads(net, xyz, vd, w, True, hip=False)
+    assert all(bool(torch.isfinite(g).all()) for g in g_h.values())
+    _, g_d, _ = _fp64(net, lambda: _grads(net, xyz.double(), vd.double(), w.double(), True, hip=False))
+    worst = _compare64(g_h, g_t, g_d)
+    print(f"row outliers, d_hidden {d_hidden}: worst HIP gradient error vs float64 {worst:.2e} of max |grad|")
+
+
 def test_volume_renderer_training_step_hip_vs_torch():
     """One train.py step (renderers.VolumeRenderer module path, MSE on rgb
     coarse + fine) with the HIP field backward vs the PyTorch graph, every
